@@ -1,10 +1,19 @@
 """Filter-build benchmark (BASELINE.json metric: filter-build Mkeys/s, device-resident,
 16-byte keys @ 10 bits/key, bit-exact).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
                   [--workload bloom10|bloom12|vqf12|probe10|probe_vqf12|bloom10k24|vqf12k24|
                               bloom10var|vqf12var|bloom12big|bloom10mono|bloom10monok24|bloom12hash]
                   [--total-keys T]
+
+A plain run does only what the headline figure needs: it generates the keys, ramps the clock,
+warms up, times the K steps, writes the timed path's last output if `--dump-outputs DIR` is
+given (DIR/<name>.npy, float32; see dump_outputs) and prints the JSON line (`metric`, `value`,
+`unit`, `ms_per_step`, the `roofline` figures of the timed launches, ...).  Everything below
+that runs after the timed region -- the oracle comparisons ("verified"), the CPU baseline, the
+end-to-end PCIe leg, the separately timed all-gather and its check, the pipelined figure, the
+stage breakdowns of `--chunks` and bloom12hash, `--sweep` -- runs only with `--full`
+(`--no-verify`, `--no-cpu-baseline` and `--no-e2e` then drop single legs of it).
 
 One step = one pass of the hot path over one batch: build every leaf filter of
 `--keys-per-gpu` (default 100M, BASELINE config 2) 16-byte keys held in HBM, S = 16,384 keys
@@ -80,6 +89,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline "
+                         "figure: the oracle comparison of the timed output, the CPU baseline, "
+                         "the end-to-end PCIe leg, the all-gather timing and check, the pipelined "
+                         "figure, stage breakdowns, --sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as "
+                         "DIR/<name>.npy (float32; a seeded sample of the bytes and byte sums "
+                         "over the whole array)")
     ap.add_argument("--workload", default="bloom10", choices=sorted(WORKLOADS))
     ap.add_argument("--keys-per-gpu", type=int, default=100_000_000)
     ap.add_argument("--leaf-keys", type=int, default=None,
@@ -121,7 +139,12 @@ def parse():
                          "timing")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (0: every core this process may use)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.sweep and not args.full:
+        ap.error("--sweep is one of the --full legs: pass --full with it")
+    if not args.full:  # a plain run ends with the timed steps
+        args.no_verify = args.no_cpu_baseline = args.no_e2e = True
+    return args
 
 
 # ---------------------------------------------------------------------------------------
@@ -357,7 +380,7 @@ def main():
     out = torch.zeros(plan.total_out_bytes, dtype=torch.uint8, device=dev)
     ws = torch.empty(max(plan.workspace_bytes, 1), dtype=torch.uint8, device=dev)
     gathered = (torch.empty(plan.total_out_bytes * world, dtype=torch.uint8, device=dev)
-                if pg else None)
+                if pg and (args.full or args.allgather) else None)
 
     probe = args.workload.startswith("probe")
     if probe:
@@ -415,6 +438,13 @@ def main():
     units = 2 * total_keys if probe else total_keys
     ms_per_step = wall / args.steps * 1e3
     value = units * args.steps / wall / 1e6
+    if args.dump_outputs:
+        if probe:
+            dump_outputs(args.dump_outputs, world, rank, probe_results=res)
+        elif args.allgather and pg:
+            dump_outputs(args.dump_outputs, world, rank, gathered_filters=gathered)
+        else:
+            dump_outputs(args.dump_outputs, world, rank, filters=out)
 
     # ---- the timed output, checked (untimed) ----
     verified = None
@@ -443,12 +473,13 @@ def main():
     fpr = None
     if probe:
         alg_bytes = q.shape[0] * (16 + 4 + 1)
-        hit_res = res[is_hit]
-        if not bool(hit_res.all()):
-            bad = torch.nonzero(hit_res == 0).flatten()
-            raise SystemExit(f"false negatives in the probe: {bad.numel()} of {hit_res.numel()} "
-                             f"hits, first indices {bad[:8].tolist()}")
-        fpr = float(res[~is_hit].float().mean())
+        if args.full:
+            hit_res = res[is_hit]
+            if not bool(hit_res.all()):
+                bad = torch.nonzero(hit_res == 0).flatten()
+                raise SystemExit(f"false negatives in the probe: {bad.numel()} of "
+                                 f"{hit_res.numel()} hits, first indices {bad[:8].tolist()}")
+            fpr = float(res[~is_hit].float().mean())
     else:
         key_in = n * key_bytes if offsets is None else keys.numel() + 8 * (n + 1)
         alg_bytes = key_in + int(plan.segs["payload_bytes"].astype(np.int64).sum())
@@ -471,7 +502,7 @@ def main():
 
     allgather_ms = None
     gather_ok = None
-    if pg:
+    if pg and args.full:
         progress("verified; timing the all-gather")
         if not args.allgather:
             torch.cuda.synchronize()
@@ -495,8 +526,8 @@ def main():
     # leaves dealt in block-cyclic rounds, round c gathered on a communication stream while
     # round c + 1 builds (turtle_kv_amd.dist.PipelinedLeafGather; bench --chunks K times it alone)
     pipelined = None
-    if (pg and world > 1 and not probe and key_bytes == 16 and args.workload not in MONOLITHIC
-            and not args.allgather):
+    if (args.full and pg and world > 1 and not probe and key_bytes == 16
+            and args.workload not in MONOLITHIC and not args.allgather):
         del gathered
         torch.cuda.empty_cache()
         try:
@@ -613,6 +644,40 @@ def main():
             line["probe"].update({k: v for k, v in probe_check.items() if k != "cpu_baseline"})
             line["verified"] = probe_check["results_equal_oracle"]
     print(json.dumps(line), flush=True)
+
+
+DUMP_SAMPLE_BYTES = 4 << 20   # elements of <name>.npy when the array is larger
+DUMP_MAX_PIECES = 4 << 20     # elements of <name>_piece_sums.npy at most
+
+
+def dump_outputs(out_dir, world, rank, **arrays):
+    """--dump-outputs: each uint8 device array the timed path's last step left (the filter
+    array a caller of build_all_filters receives, or the probe's answers), for comparing two
+    builds of the library output for output.  Per array, as float32 (at most 32 MB):
+      <name>.npy             the bytes themselves; of an array over 4 Mi bytes, the bytes at
+                             4 Mi sorted positions drawn once with numpy's default_rng(0)
+      <name>_piece_sums.npy  the sum of the byte values of every 64-byte piece of the WHOLE
+                             array (pieces of 128, 256, ... bytes where that keeps the pieces
+                             under 4 Mi), so any changed bit anywhere changes one sum by 2^k
+    Ranks of a multi-GPU run write <name>_rank<r>*.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        host = t.detach().reshape(-1).cpu().numpy()
+        n = host.size
+        if n > DUMP_SAMPLE_BYTES:
+            idx = np.sort(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE_BYTES))
+            sample = host[idx]
+        else:
+            sample = host
+        piece = 64
+        while -(-n // piece) > DUMP_MAX_PIECES:
+            piece *= 2
+        padded = np.zeros(-(-n // piece) * piece, np.uint8)
+        padded[:n] = host
+        sums = padded.reshape(-1, piece).sum(axis=1, dtype=np.uint32)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), sample.astype(np.float32))
+        np.save(os.path.join(out_dir, f"{name}{suffix}_piece_sums.npy"), sums.astype(np.float32))
 
 
 def reduce_max(torch, dist, x, device):
@@ -748,12 +813,19 @@ def bench_pipelined_gather(args, torch, dist, amq, world, rank, dev, kind, bpk, 
     torch.cuda.synchronize()
     wall = timed(args.steps)
     ms_per_step = wall / args.steps * 1e3
-    reps = max(1, min(5, args.steps))
-    build_ms = timed(reps, gather=False) / reps * 1e3
-    gather_ms = timed(reps, build=False) / reps * 1e3
-
-    pl.step(batches)  # the checked array: one more full step
-    torch.cuda.synchronize()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, world, rank, gathered_filters=pl.filters())
+    breakdown = None
+    if args.full:
+        reps = max(1, min(5, args.steps))
+        build_ms = timed(reps, gather=False) / reps * 1e3
+        gather_ms = timed(reps, build=False) / reps * 1e3
+        breakdown = {"build_only": round(build_ms, 4), "gather_only": round(gather_ms, 4),
+                     "pipelined": round(ms_per_step, 4),
+                     "sum_of_parts": round(build_ms + gather_ms, 4),
+                     "max_of_parts": round(max(build_ms, gather_ms), 4)}
+        pl.step(batches)  # the checked array: one more full step
+        torch.cuda.synchronize()
     gather_ok = None
     if rank == 0 and not args.no_verify:
         gather_ok = verify_gather(torch, amq, kind, bpk, cap, all_counts, stride, pl.filters(), 16,
@@ -784,10 +856,7 @@ def bench_pipelined_gather(args, torch, dist, amq, world, rank, dev, kind, bpk, 
                    "backend": args.backend, "chunk_leaves": q, "rounds": len(pl.rounds)},
         "roofline": None,
         "cpu_baseline": None,
-        "breakdown_ms": {"build_only": round(build_ms, 4), "gather_only": round(gather_ms, 4),
-                         "pipelined": round(ms_per_step, 4),
-                         "sum_of_parts": round(build_ms + gather_ms, 4),
-                         "max_of_parts": round(max(build_ms, gather_ms), 4)},
+        "breakdown_ms": breakdown,
         "allgather_bytes_in_per_gpu": (world - 1) * len(pl.rounds) * pl.round_bytes,
         "gather_verified": gather_ok,
         "comm": comm,
@@ -855,59 +924,63 @@ def bench_hash_sharded(args, torch, dist, amq, world, rank, dev, bpk, label, pg=
     progress(f"{args.steps} timed steps: {wall / args.steps * 1e3:.3f} ms per step")
     lost = hs.lost()  # blocks that needed more overflow room than they have (not for hashed keys)
 
-    # untimed breakdown: the stages one after another on rank 0 (HIP events on the current
-    # stream; each stage's collectives on the current stream, not overlapped)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-    if pg:
-        dist.barrier()
-    torch.cuda.synchronize()
-    ev[0].record()
-    if not hs.records:
-        hs.step(keys, gather=False)
-        ev[1].record()
-        ev[2].record()
-        ev[3].record()
-    else:
-        for c in range(hs.chunks):
-            hs.route_chunk(keys, c)
-        ev[1].record()
-        if pg and world > 1:
-            for c in range(hs.chunks):
-                hs.exchange_chunk(c)
-        ev[2].record()
-        for j in range(hs.g):
-            hs.build_part(j)
-        ev[3].record()
-    if pg:
-        if hs.records:
-            for j in range(hs.g):
-                hs.gather_round(j)
-        else:
-            hs.allgather()
-    ev[4].record()
-    torch.cuda.synchronize()
-    route_ms, a2a_ms, build_ms, gather_ms = (ev[i].elapsed_time(ev[i + 1]) for i in range(4))
-    # one more pipelined step with an event at every stage boundary: when each chunk's route,
-    # each round's exchange, each part build and each round's gather ended on its stream
-    timeline = None
-    if hs.records:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, world, rank,
+                     filter=hs.filter() if hs.records or gather_in_step else hs.allgather())
+
+    route_ms = a2a_ms = build_ms = gather_ms = timeline = allgather_ms = None
+    if args.full:
+        # untimed breakdown: the stages one after another on rank 0 (HIP events on the current
+        # stream; each stage's collectives on the current stream, not overlapped)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
         if pg:
             dist.barrier()
-        hs.step(keys, gather=gather_in_step, timeline=True)
         torch.cuda.synchronize()
-        timeline = hs.timeline_ms()
+        ev[0].record()
+        if not hs.records:
+            hs.step(keys, gather=False)
+            ev[1].record()
+            ev[2].record()
+            ev[3].record()
+        else:
+            for c in range(hs.chunks):
+                hs.route_chunk(keys, c)
+            ev[1].record()
+            if pg and world > 1:
+                for c in range(hs.chunks):
+                    hs.exchange_chunk(c)
+            ev[2].record()
+            for j in range(hs.g):
+                hs.build_part(j)
+            ev[3].record()
+        if pg:
+            if hs.records:
+                for j in range(hs.g):
+                    hs.gather_round(j)
+            else:
+                hs.allgather()
+        ev[4].record()
+        torch.cuda.synchronize()
+        route_ms, a2a_ms, build_ms, gather_ms = (ev[i].elapsed_time(ev[i + 1]) for i in range(4))
+        # one more pipelined step with an event at every stage boundary: when each chunk's route,
+        # each round's exchange, each part build and each round's gather ended on its stream
+        if hs.records:
+            if pg:
+                dist.barrier()
+            hs.step(keys, gather=gather_in_step, timeline=True)
+            torch.cuda.synchronize()
+            timeline = hs.timeline_ms()
 
-    allgather_ms = None
-    if pg and not gather_in_step:
-        dist.barrier()
-        g0 = time.perf_counter()
-        for _ in range(3):
-            hs.allgather()
+        if pg and not gather_in_step:
+            dist.barrier()
+            g0 = time.perf_counter()
+            for _ in range(3):
+                hs.allgather()
+            torch.cuda.synchronize()
+            allgather_ms = reduce_max(torch, dist, (time.perf_counter() - g0) / 3 * 1e3, coll_dev)
+        filt = hs.filter() if hs.records else hs.allgather()
         torch.cuda.synchronize()
-        allgather_ms = reduce_max(torch, dist, (time.perf_counter() - g0) / 3 * 1e3, coll_dev)
-    filt = hs.filter() if hs.records else hs.allgather()
-    torch.cuda.synchronize()
-    progress("breakdown and all-gather done; verifying")
+        progress("breakdown and all-gather done; verifying")
     comm = comm_info(torch, dist, dev) if pg else None
 
     check = None
@@ -974,7 +1047,8 @@ def bench_hash_sharded(args, torch, dist, amq, world, rank, dev, bpk, label, pg=
                                     "allgather": round(gather_ms, 4),
                                     "note": "the routed form's stages one after another (untimed "
                                             "by value" + ("; the timed step is the direct range "
-                                                          "build)" if hs._direct else ")")},
+                                                          "build)" if hs._direct else ")")}
+        if args.full else None,
         "step_timeline_rank0_ms": timeline,
         "verified": check["ok"] if check else None, "verify": check,
     }

@@ -36,7 +36,71 @@ def test_bench_refuses_world_mismatch():
     assert "--gpus 2 but WORLD_SIZE=1" in r.stderr
 
 
-SMALL = ["--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--no-e2e", "--no-cpu-baseline"]
+def test_dump_outputs_sample_and_piece_sums(tmp_path):
+    """--dump-outputs' writer on host arrays: a small array is written whole, a large one as the
+    same seeded sample every time, and the piece sums cover every byte (one changed bit past the
+    sample's reach changes exactly one sum)."""
+    import numpy as np
+    import torch
+
+    import bench
+    rng = np.random.default_rng(1)
+    small = rng.integers(0, 256, 1000, dtype=np.uint8)
+    big = rng.integers(0, 256, bench.DUMP_SAMPLE_BYTES + 12345, dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), 1, 0, small=torch.from_numpy(small),
+                       big=torch.from_numpy(big))
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.astype(np.float32))
+    sums = np.load(tmp_path / "a" / "small_piece_sums.npy")
+    assert sums.dtype == np.float32 and sums.shape == (16,)
+    assert np.array_equal(sums, np.pad(small, (0, 24)).reshape(16, 64).sum(1))
+    b = np.load(tmp_path / "a" / "big.npy")
+    assert b.dtype == np.float32 and b.shape == (bench.DUMP_SAMPLE_BYTES,)
+    bsums = np.load(tmp_path / "a" / "big_piece_sums.npy")
+    assert bsums.sum(dtype=np.float64) == big.sum(dtype=np.uint64)
+
+    changed = big.copy()
+    changed[-1] ^= 0x10
+    bench.dump_outputs(str(tmp_path / "b"), 2, 1, big=torch.from_numpy(changed))
+    b2 = np.load(tmp_path / "b" / "big_rank1.npy")
+    drawn = np.sort(np.random.default_rng(0).integers(0, big.size, bench.DUMP_SAMPLE_BYTES))
+    assert np.array_equal(b2 != b, drawn == big.size - 1)  # only draws of the changed byte
+    d = np.load(tmp_path / "b" / "big_rank1_piece_sums.npy") - bsums
+    assert np.count_nonzero(d) == 1 and abs(d[-1]) == 0x10
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_timed_output(tmp_path):
+    """A plain run: the timed steps and nothing after them (no oracle legs in the line), and
+    --dump-outputs writes the filter array the last timed step built: its piece sums equal
+    those of the same build done here."""
+    import numpy as np
+    import torch
+
+    import bench
+    import turtle_kv_amd as amq
+    r = run_bench("--keys-per-gpu", "3000001", "--steps", "4", "--warmup", "1", "--ramp-ms", "0",
+                  "--dump-outputs", str(tmp_path / "o"))
+    assert r.returncode == 0, r.stderr[-4000:]
+    d = last_json(r)
+    assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["unit"] == "Mkeys/s"
+    assert d["cpu_baseline"] is None
+    assert not {"verify", "verified", "e2e_pcie_inclusive", "batch_sweep"} & set(d)
+    from turtle_kv_amd import dist as tdist
+    counts = bench.segment_counts(3_000_001)   # 183 full leaves and one of 1,729 keys
+    plan = amq.plan_filters(amq.BLOOM, counts, 10,
+                            out_stride=tdist.leaf_stride(amq.BLOOM, 10, max(counts)))
+    keys = amq.gen_keys16(42, 0, 3_000_001, device=torch.device("cuda", 0))
+    out = torch.zeros(plan.total_out_bytes, dtype=torch.uint8, device=keys.device)
+    amq.build_all_filters(plan, amq.KeyBatch.fixed(keys), out=out)
+    bench.dump_outputs(str(tmp_path / "here"), 1, 0, filters=out)
+    for name in ("filters.npy", "filters_piece_sums.npy"):
+        got, ref = np.load(tmp_path / "o" / name), np.load(tmp_path / "here" / name)
+        assert got.dtype == np.float32 and np.array_equal(got, ref), name
+
+
+# --full: the oracle checks, the all-gather timing and the stage breakdowns these tests read
+SMALL = ["--full", "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--no-e2e", "--no-cpu-baseline"]
 
 
 @pytest.mark.gpu
@@ -84,7 +148,7 @@ def test_bench_strong_scaling_two_ranks():
 def test_bench_probe_matches_oracle(workload):
     """Config 4's check at a small size: every answer equals the oracle's over the GPU-built
     filter, so the FPRs are equal; the probe line carries a CPU baseline."""
-    r = run_bench("--workload", workload, "--keys-per-gpu", "1000000", "--steps", "3",
+    r = run_bench("--full", "--workload", workload, "--keys-per-gpu", "1000000", "--steps", "3",
                   "--warmup", "1", "--ramp-ms", "0", "--no-e2e")
     assert r.returncode == 0, r.stderr[-4000:]
     d = last_json(r)
@@ -98,8 +162,8 @@ def test_bench_probe_matches_oracle(workload):
 def test_bench_single_gpu_line():
     """The default line's shape at a small size: verified sample, batch-size sweep, a CPU
     baseline with the host's CPU share stated."""
-    r = run_bench("--keys-per-gpu", "3000000", "--steps", "3", "--warmup", "1", "--ramp-ms", "0",
-                  "--no-e2e", "--sweep")
+    r = run_bench("--full", "--keys-per-gpu", "3000000", "--steps", "3", "--warmup", "1",
+                  "--ramp-ms", "0", "--no-e2e", "--sweep")
     assert r.returncode == 0, r.stderr[-4000:]
     d = last_json(r)
     assert d["n_gpus"] == 1 and d["verified"] is True
@@ -115,7 +179,7 @@ def test_bench_two_ranks_gloo_host_legs():
     """N > 1 lines carry the north star's host figures: every rank runs its own end-to-end
     leg (its pages back to host page memory over its own link) at the same time, and rank 0
     times the CPU baseline after the other ranks have left."""
-    r = run_bench("--gpus", "2", "--backend", "gloo", "--keys-per-gpu", "2000000",
+    r = run_bench("--full", "--gpus", "2", "--backend", "gloo", "--keys-per-gpu", "2000000",
                   "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--cpu-threads", "4")
     assert r.returncode == 0, r.stderr[-4000:]
     d = last_json(r)
@@ -199,8 +263,8 @@ def test_bench_probe_full_size(workload):
     """Config 4 at its own size in the GPU suite: 200M shuffled hit/miss lookups against the
     100M-key build, every answer equal to the oracle's over the GPU-built filter bytes, so the
     FPRs are equal; no false negatives."""
-    r = run_bench("--workload", workload, "--steps", "3", "--warmup", "1", "--ramp-ms", "0",
-                  "--no-e2e", "--no-cpu-baseline", timeout=600)
+    r = run_bench("--full", "--workload", workload, "--steps", "3", "--warmup", "1",
+                  "--ramp-ms", "0", "--no-e2e", "--no-cpu-baseline", timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     d = last_json(r)
     p = d["probe"]

@@ -20,7 +20,7 @@ if [ "$1" != "run" ]; then
 fi
 cd $R; mkdir -p gpurun_out
 for e in $EXPS; do
-  TKV_AMQ_LIB=$R/tools/exp/libtkv_amq_exp$e.so timeout -k 10 200 python bench.py --workload ${W:-vqf12} \
+  TKV_AMQ_LIB=$R/tools/exp/libtkv_amq_exp$e.so timeout -k 10 200 python bench.py --full --workload ${W:-vqf12} \
     --no-cpu-baseline --no-e2e --steps 20 > gpurun_out/exp_$e.log 2>&1 || exit 3
   echo "exp $e: $(python -c "import json;l=json.loads(open('gpurun_out/exp_$e.log').read().strip().splitlines()[-1]);print(l['value'], l['roofline']['kernel_ms'])")"
 done

@@ -14,25 +14,25 @@ if has tests; then
   timeout -k 10 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1 || exit 2
 fi
 if has bench; then
-  timeout -k 10 300 python bench.py > $O/bench_bloom10.log 2>&1 || exit 3
-  timeout -k 10 300 python bench.py --workload vqf12 --no-e2e > $O/bench_vqf12.log 2>&1 || exit 4
-  timeout -k 10 300 python bench.py --workload probe10 > $O/bench_probe10.log 2>&1 || exit 5
-  timeout -k 10 300 python bench.py --workload probe_vqf12 > $O/bench_probe_vqf12.log 2>&1 || exit 6
-  timeout -k 10 300 python bench.py --workload bloom12 --no-e2e > $O/bench_bloom12.log 2>&1 || exit 7
-  timeout -k 10 300 python bench.py --workload bloom10k24 > $O/bench_bloom10k24.log 2>&1 || exit 8
-  timeout -k 10 300 python bench.py --workload vqf12k24 > $O/bench_vqf12k24.log 2>&1 || exit 8
-  timeout -k 10 300 python bench.py --workload bloom12 --total-keys 1000000000 --steps 10 --no-e2e > $O/bench_bloom12_1B.log 2>&1 || exit 9
-  timeout -k 10 300 python bench.py --workload bloom10mono > $O/bench_bloom10mono.log 2>&1 || exit 10
-  timeout -k 10 300 python bench.py --workload bloom10monok24 > $O/bench_bloom10monok24.log 2>&1 || exit 10
-  timeout -k 10 300 python bench.py --workload bloom10var --no-e2e > $O/bench_bloom10var.log 2>&1 || exit 10
-  timeout -k 10 300 python bench.py --workload bloom12hash > $O/bench_bloom12hash.log 2>&1 || exit 10
-  timeout -k 10 300 python bench.py --workload vqf12var --no-e2e > $O/bench_vqf12var.log 2>&1 || exit 10
-  timeout -k 10 300 python bench.py --workload bloom12big --no-e2e > $O/bench_bloom12big.log 2>&1 || exit 10
+  timeout -k 10 300 python bench.py --full > $O/bench_bloom10.log 2>&1 || exit 3
+  timeout -k 10 300 python bench.py --full --workload vqf12 --no-e2e > $O/bench_vqf12.log 2>&1 || exit 4
+  timeout -k 10 300 python bench.py --full --workload probe10 > $O/bench_probe10.log 2>&1 || exit 5
+  timeout -k 10 300 python bench.py --full --workload probe_vqf12 > $O/bench_probe_vqf12.log 2>&1 || exit 6
+  timeout -k 10 300 python bench.py --full --workload bloom12 --no-e2e > $O/bench_bloom12.log 2>&1 || exit 7
+  timeout -k 10 300 python bench.py --full --workload bloom10k24 > $O/bench_bloom10k24.log 2>&1 || exit 8
+  timeout -k 10 300 python bench.py --full --workload vqf12k24 > $O/bench_vqf12k24.log 2>&1 || exit 8
+  timeout -k 10 300 python bench.py --full --workload bloom12 --total-keys 1000000000 --steps 10 --no-e2e > $O/bench_bloom12_1B.log 2>&1 || exit 9
+  timeout -k 10 300 python bench.py --full --workload bloom10mono > $O/bench_bloom10mono.log 2>&1 || exit 10
+  timeout -k 10 300 python bench.py --full --workload bloom10monok24 > $O/bench_bloom10monok24.log 2>&1 || exit 10
+  timeout -k 10 300 python bench.py --full --workload bloom10var --no-e2e > $O/bench_bloom10var.log 2>&1 || exit 10
+  timeout -k 10 300 python bench.py --full --workload bloom12hash > $O/bench_bloom12hash.log 2>&1 || exit 10
+  timeout -k 10 300 python bench.py --full --workload vqf12var --no-e2e > $O/bench_vqf12var.log 2>&1 || exit 10
+  timeout -k 10 300 python bench.py --full --workload bloom12big --no-e2e > $O/bench_bloom12big.log 2>&1 || exit 10
 fi
 if has sweep; then
   # batch-size curve (first 64 / 256 / 1024 leaves of the same keys), and the per-leaf call sizes
   for W in bloom10 vqf12; do
-    timeout -k 10 300 python bench.py --workload $W --sweep --no-e2e --no-cpu-baseline > $O/sweep_$W.log 2>&1 || exit 14
+    timeout -k 10 300 python bench.py --full --workload $W --sweep --no-e2e --no-cpu-baseline > $O/sweep_$W.log 2>&1 || exit 14
   done
   timeout -k 10 300 python tools/small_batch.py --kind 0 > $O/small_bloom10.log 2>&1 || exit 15
   timeout -k 10 300 python tools/small_batch.py --kind 1 > $O/small_vqf12.log 2>&1 || exit 15
