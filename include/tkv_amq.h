@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TKV_AMQ_ABI_VERSION 2
+#define TKV_AMQ_ABI_VERSION 3
 
 /* status codes (batt::StatusCode values) */
 #define TKV_AMQ_OK 0
@@ -185,7 +185,8 @@ int tkv_amq_build(int kind, const uint8_t* keys, const uint64_t* key_offsets,
  * 177-215 sizes any leaf) through the tiled build, up to 40 of them per launch, and the other
  * leaves through the batch kernels; with other key shapes (variable-length, other strides) only
  * the leaves past 16 windows (2.5 MB) leave the batch kernels, each hashed into bit records by
- * a pass of its own and built by the tiled build (k <= 8; above, device atomics); tkv_amq_build
+ * a pass of its own and built by the tiled build (k <= 16, i.e. up to 23 bits/key, two records
+ * per key above k = 8: the wide record below; from k = 17, device atomics); tkv_amq_build
  * of such a batch sets those leaves' bits with device atomics.  The workspace tkv_amq_plan
  * sizes covers either key shape.
  * h_segs == NULL, a single leaf, or a batch without such leaves: exactly tkv_amq_build. */
@@ -237,7 +238,8 @@ int tkv_amq_bloom_build_range(const uint8_t* d_keys16, uint64_t n_keys, const tk
                               uint8_t* d_out, void* d_workspace, uint64_t workspace_bytes,
                               void* stream);
 
-/* The same two steps with 12-byte bit records in place of the keys (hash_count <= 8, i.e.
+/* The same two steps with 12-byte bit records in place of the keys (the routes of 16- and
+ * 24-byte keys: hash_count <= 8, i.e.
  * bits_per_key <= 12; InvalidArgument otherwise): tkv_amq_bloom_route_records hashes each key
  * once and writes its record (block in tile, the k bit indices, the tile relative to its
  * owner's first tile) into d_recs12 ordered by owner, so the all-to-all carries 12 bytes per key
@@ -260,6 +262,8 @@ int tkv_amq_bloom_route_records_ex(const uint8_t* d_keys, uint32_t key_bytes, ui
                                    uint32_t hash_count, uint32_t n_parts, uint8_t* d_recs12,
                                    uint32_t* d_part_counts, void* d_workspace,
                                    uint64_t workspace_bytes, void* stream);
+/* tkv_amq_bloom_build_range_records takes hash_count up to 16: n_recs counts records, and
+ * every record of a hash_count > 8 build sets its eight indices (wide records, below). */
 uint64_t tkv_amq_bloom_build_range_records_ws_bytes(uint64_t n_recs, uint32_t tile_begin,
                                                     uint32_t tile_end);
 int tkv_amq_bloom_build_range_records(const uint8_t* d_recs12, uint64_t n_recs,
@@ -267,6 +271,31 @@ int tkv_amq_bloom_build_range_records(const uint8_t* d_recs12, uint64_t n_recs,
                                       uint32_t hash_count, uint32_t tile_begin, uint32_t tile_end,
                                       uint8_t* d_out, void* d_workspace, uint64_t workspace_bytes,
                                       void* stream);
+
+/* The wide record, and the route for keys of any shape.  A record holds eight bit indices; a
+ * key with 9 <= hash_count <= 16 (13 to 23 bits/key) leaves as TWO 12-byte records with the
+ * same block and tile, the first holding bits 0..7, the second bits 8..k-1 padded by repeating
+ * bit 8 (OR is idempotent: the padding sets no new bit).  So the exchange still carries
+ * 12-byte units, the 6,400-tile limit per part is unchanged, and a record consumer sets all
+ * eight indices of every record without knowing k.
+ * tkv_amq_bloom_route_records_any routes keys of any shape -- key_offsets == NULL: a fixed
+ * key_stride (> 0, 16 and 24 included); else key_offsets[n_keys + 1] on the device, as
+ * tkv_amq_build takes them -- for 1 <= hash_count <= 16.  The rank's keys are keys [0, n_keys)
+ * of its own buffer (the segment's key_begin and n_keys describe the whole filter and are not
+ * applied).  Each key becomes rpk = tkv_amq_bloom_records_per_key(hash_count) records, written
+ * to d_recs12 (rpk * n_keys * 12 bytes, 4-byte aligned) grouped by part, part 0 first;
+ * d_part_counts[n_parts] counts RECORDS.  A key's records land in the same part.  Asynchronous,
+ * allocates nothing, capturable.  InvalidArgument: hash_count 0 or > 16, n_parts 0 or > 2048,
+ * parts of more than tkv_amq_bloom_range_max_tiles(1) tiles, rpk * n_keys > 0xffffffff, fixed
+ * keys with stride 0, null or misaligned buffers, a short workspace. */
+/* 12-byte bit records per key: 1 for hash_count 1..8, 2 for 9..16, 0 otherwise (host only) */
+uint32_t tkv_amq_bloom_records_per_key(uint32_t hash_count);
+uint64_t tkv_amq_bloom_route_records_any_ws_bytes(uint64_t n_keys, uint32_t n_parts, uint32_t hash_count);
+int tkv_amq_bloom_route_records_any(const uint8_t* keys, const uint64_t* key_offsets, uint32_t key_stride,
+                                    uint64_t n_keys, const tkv_amq_segment* d_seg, uint32_t n_blocks,
+                                    uint32_t hash_count, uint32_t n_parts, uint8_t* d_recs12,
+                                    uint32_t* d_part_counts, void* d_workspace, uint64_t workspace_bytes,
+                                    void* stream);
 
 /* The pipelined hash-range build (hash_count <= 8): the route writes fixed-capacity part
  * blocks, so the exchange needs no counts first.  Parts of q tiles are owned round-robin: part p

@@ -1,8 +1,9 @@
 """Build rate of single Bloom filters past four LDS windows (the tiled monolithic build) and of
 batches holding leaves past 16 windows (tkv_amq_build_ex: those leaves built together through
-the tiled build, the others batched), @10 bits/key, HIP events, 20 reps.  --shape var / k20:
-variable-length keys of 8-31 bytes, or 20-byte keys (random bytes made on the device), whose
-leaves past 16 windows take bloom_part_any (round 5: device atomics)."""
+the tiled build, the others batched), at --bpk bits/key (default 10), HIP events, 20 reps.
+--shape var / k20: variable-length keys of 8-31 bytes, or 20-byte keys (random bytes made on the
+device), whose leaves past 16 windows take bloom_any_records and the tiled build (round 5:
+device atomics) -- up to 23 bits/key, above 12 as wide records (two records per key)."""
 import os
 import sys
 import time
@@ -38,6 +39,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="k16", help="k16, var, or kN (N-byte keys)")
     ap.add_argument("--only", default=None, help="run the cases whose name contains this")
+    ap.add_argument("--bpk", type=int, default=10, help="bits per key")
     args = ap.parse_args()
     cases = [("one filter of 1M", [1_000_000]),
              ("one filter of 3M", [3_000_000]),
@@ -52,7 +54,7 @@ def main():
     for name, counts in cases:
         n = sum(counts)
         kb = make_keys(torch, amq, args.shape, n)
-        plan = amq.plan_filters(amq.BLOOM, counts, 10)
+        plan = amq.plan_filters(amq.BLOOM, counts, args.bpk)
         out = torch.empty(plan.total_out_bytes, dtype=torch.uint8, device="cuda")
         ws = torch.empty(max(1, plan.workspace_bytes), dtype=torch.uint8, device="cuda")
         for _ in range(3):
@@ -69,7 +71,7 @@ def main():
         ms = float(np.median([a.elapsed_time(b) for a, b in ev]))
         # (host_us: the enqueue time per call; when it is above the events' time, the host and
         # not the device sets the rate of back-to-back calls)
-        print(f"{args.shape} {name}: {n} keys, {ms * 1e3:.1f} us, {n / ms / 1e6:.1f} Gkeys/s "
+        print(f"{args.shape} @{args.bpk} {name}: {n} keys, {ms * 1e3:.1f} us, {n / ms / 1e6:.1f} Gkeys/s "
               f"(host enqueue {host_us:.1f} us per call)", flush=True)
         del kb, out, ws
         torch.cuda.empty_cache()

@@ -91,6 +91,8 @@ EXPORTS = [
     "tkv_amq_bloom_route_records_ex", "tkv_amq_bloom_tile_blocks", "tkv_amq_bloom_range_max_tiles",
     "tkv_amq_bloom_route_plan", "tkv_amq_bloom_route_blocks", "tkv_amq_bloom_build_part_blocks",
     "tkv_amq_bloom_blocks_lost", "tkv_amq_build_ex",
+    "tkv_amq_bloom_records_per_key", "tkv_amq_bloom_route_records_any_ws_bytes",
+    "tkv_amq_bloom_route_records_any",
 ]
 
 
@@ -216,6 +218,13 @@ def lib(build_if_missing: bool = True):
         L.tkv_amq_bloom_build_range_records_ws_bytes.argtypes = [u64, u32, u32]
         L.tkv_amq_bloom_build_range_records.restype = i32
         L.tkv_amq_bloom_build_range_records.argtypes = [vp, u64, vp, u32, u32, u32, u32, vp, vp, u64, vp]
+    if hasattr(L, "tkv_amq_bloom_route_records_any"):
+        L.tkv_amq_bloom_records_per_key.restype = u32
+        L.tkv_amq_bloom_records_per_key.argtypes = [u32]
+        L.tkv_amq_bloom_route_records_any_ws_bytes.restype = u64
+        L.tkv_amq_bloom_route_records_any_ws_bytes.argtypes = [u64, u32, u32]
+        L.tkv_amq_bloom_route_records_any.restype = i32
+        L.tkv_amq_bloom_route_records_any.argtypes = [vp, vp, u32, u64, vp, u32, u32, u32, vp, vp, vp, u64, vp]
     if hasattr(L, "tkv_amq_bloom_route_plan"):
         prp = ctypes.POINTER(RoutePlan)
         L.tkv_amq_bloom_route_plan.restype = i32

@@ -990,6 +990,11 @@ __global__ __launch_bounds__(256) void bloom_global_set(const uint8_t* __restric
 // The tile field is the tile relative to the record's part (routed records); a partition's
 // own region records leave it unused.  Overflow entries are 16 bytes: the record and its
 // tile (relative to the build's first tile), or the 16-byte key.
+// Wide record (9 <= k <= 16; keys of any shape: bloom_any_records, route_any): the key leaves
+// as two records with the same block and tile, the first holding b0..b7, the second
+// b8..b(k-1) padded with b8.  OR is idempotent, so every consumer sets all eight indices of
+// every record of such a build without knowing k, and a key's two records need not stay
+// together.  Whether a k > 8 launch holds records or 16-byte keys is PartGeom::rb (12 or 16).
 // ---------------------------------------------------------------------------------------
 constexpr uint32_t kTileBlocks = 2048;   // 128 KiB LDS image per tile
 constexpr uint32_t kTileShift = 11;
@@ -1166,29 +1171,78 @@ __device__ inline uint32_t rec_hash_bits(const Key24& kv, uint32_t nb, uint32_t 
   return (uint32_t)__umul64hi(h0, (uint64_t)nb);
 }
 
-// a key of any other shape (bloom_any_records): its bytes and length
-struct KeyRef {
-  const uint8_t* p;
-  uint32_t len;
-};
+// 12-byte records per key: one up to k = 8, two (a wide record) up to k = 16, 0: none
+__host__ __device__ constexpr inline uint32_t bloom_rpk(uint32_t k) { return k == 0 || k > 16 ? 0u : (k <= 8 ? 1u : 2u); }
 
-// its block and bit indices (k <= 8): under 32 bytes the seed-independent lane rounds are
-// shared by the k hashes (XxhShort), longer keys hash from scratch per seed
-__device__ inline uint32_t rec_hash_bits_any(const KeyRef& kr, uint32_t nb, uint32_t k, uint32_t (&b)[8])
+// b_j of a key's NB (8 or 16) record indices: hash j below k, else the padding (b_0 in the
+// first record, b_8 in the second)
+template <int NB, typename F>
+__device__ inline void any_fill_bits(uint32_t k, uint32_t (&b)[NB], F&& hash_j)
+{
+#pragma unroll
+  for (uint32_t j = 1; j < (uint32_t)NB; ++j) b[j] = j < k ? hash_j(j) & 511u : b[j <= 8 ? 0 : 8];
+}
+
+// A key of any shape: its block and its NB bit indices (NB = 8: k <= 8; NB = 16: the two halves
+// of a wide record; NB = 0: the block alone, the route's count pass).  Under 32 bytes the
+// seed-independent lane rounds are shared by the k hashes (XxhShort) and, when the resource
+// covers the key array (vr.nrec), the key is read as one 32-byte window (two 16-byte loads;
+// KeyWin, as the VQF producers read them) instead of its lanes, tail word and tail bytes one
+// load each; longer keys hash from scratch per seed.
+template <int NB>
+__device__ inline uint32_t any_hash_bits(const uint8_t* keys, const VarRsrc& vr, const uint8_t* p, uint32_t len,
+                                         uint32_t nb, uint32_t k, uint32_t (&b)[NB ? NB : 1])
 {
   uint64_t h0;
-  if (kr.len < 32) {
-    const XxhShort x(kr.p, kr.len);
+  if (len < 32 && vr.nrec) {
+    KeyWin kw;
+    key_win_load(vr, (uint32_t)(p - keys - vr.base), kw);
+    uint64_t l[3];
+    uint32_t t4, tb;
+    key_win_parts(kw, len, l, t4, tb);
+    const XxhShort x(len, l, t4, tb);
     h0 = x.finish(c_bloom.seed_p5[0]);
-    b[0] = (uint32_t)h0 & 511u;
-#pragma unroll
-    for (uint32_t j = 1; j < 8; ++j) b[j] = j < k ? x.finish_lo9(c_bloom.seed_p5[j]) & 511u : b[0];
+    if constexpr (NB != 0) {
+      b[0] = (uint32_t)h0 & 511u;
+      any_fill_bits<NB>(k, b, [&](uint32_t j) { return x.finish_lo9(c_bloom.seed_p5[j]); });
+    }
+  } else if (len < 32) {
+    const XxhShort x(p, len);
+    h0 = x.finish(c_bloom.seed_p5[0]);
+    if constexpr (NB != 0) {
+      b[0] = (uint32_t)h0 & 511u;
+      any_fill_bits<NB>(k, b, [&](uint32_t j) { return x.finish_lo9(c_bloom.seed_p5[j]); });
+    }
   } else {
-    h0 = xxh64_bytes(kr.p, kr.len, c_bloom.seed[0]);
-    b[0] = (uint32_t)h0 & 511u;
-    for (uint32_t j = 1; j < 8; ++j) b[j] = j < k ? (uint32_t)xxh64_bytes(kr.p, kr.len, c_bloom.seed[j]) & 511u : b[0];
+    h0 = xxh64_bytes(p, len, c_bloom.seed[0]);
+    if constexpr (NB != 0) {
+      b[0] = (uint32_t)h0 & 511u;
+      for (uint32_t j = 1; j < (uint32_t)NB; ++j)
+        b[j] = j < k ? (uint32_t)xxh64_bytes(p, len, c_bloom.seed[j]) & 511u : b[j <= 8 ? 0 : 8];
+    }
   }
   return (uint32_t)__umul64hi(h0, (uint64_t)nb);
+}
+
+// the RPK records of a key from its block (tile `tile` of the records' build or part) and bits
+__device__ inline void rec_store(uint32_t* recs, uint64_t slot, uint32_t blk_in_tile, uint32_t tile,
+                                 const uint32_t (&b)[8])
+{
+  uint3 v;
+  rec_pack(blk_in_tile, tile, b, v.x, v.y, v.z);
+  reinterpret_cast<uint3*>(recs)[slot] = v;
+}
+
+template <int RPK>
+__device__ inline void rec_store_key(uint32_t* recs, uint64_t slot, uint32_t blk_in_tile, uint32_t tile,
+                                     const uint32_t (&b)[8 * RPK])
+{
+  const uint32_t lo[8] = {b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7]};
+  rec_store(recs, slot, blk_in_tile, tile, lo);
+  if constexpr (RPK == 2) {
+    const uint32_t hi[8] = {b[8], b[9], b[10], b[11], b[12], b[13], b[14], b[15]};
+    rec_store(recs, slot + 1, blk_in_tile, tile, hi);
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1389,6 +1443,55 @@ __global__ __launch_bounds__(NT) void route_recs(const uint8_t* __restrict__ key
   if (k == 7) route_recs_body<NT, 7, KB>(keys, sg, n_parts, per, n, q, out, s_part);
   else if (k == 8) route_recs_body<NT, 8, KB>(keys, sg, n_parts, per, n, q, out, s_part);
   else route_recs_body<NT, 0, KB>(keys, sg, n_parts, per, n, q, out, s_part);
+}
+
+// The route for keys of any shape (variable-length through offs, or any fixed stride) and
+// 1 <= k <= 16, hashing twice as the 16/24-byte route does: PASS 0 takes h0 alone (the key's
+// part; RPK slots counted per key), the scans are the same, PASS 1 hashes the key into its RPK
+// records (the tile relative to the part) and writes them side by side at the key's slot.
+// Keys [0, n) of the caller's buffer; a workgroup's keys through a buffer resource of its own
+// range, so a buffer past 2 GiB still reads windows.
+template <int PASS, int MODE, int RPK, uint32_t NT>
+__global__ __launch_bounds__(NT) void route_any(const uint8_t* __restrict__ keys, const uint64_t* __restrict__ offs,
+                                                uint32_t stride, const tkv_amq_segment* __restrict__ segs,
+                                                uint32_t* __restrict__ ws, uint32_t n_parts, uint32_t per,
+                                                uint32_t n, uint32_t q, uint32_t* __restrict__ out)
+{
+  extern __shared__ uint32_t s_part[];
+  const tkv_amq_segment sg = segs[0];
+  const uint32_t tid = threadIdx.x, w = blockIdx.x, nb = sg.n_blocks, k = sg.hash_count;
+  uint32_t* H = ws + (uint64_t)w * n_parts;
+  const uint32_t* base = ws + (uint64_t)gridDim.x * n_parts + n_parts;
+  for (uint32_t t = tid; t < n_parts; t += NT) s_part[t] = PASS == 0 ? 0u : base[t] + H[t];
+  __syncthreads();
+  const uint32_t b = min(n, w * per), e = min(n, b + per);
+  // (the count pass does not depend on k; a segment whose k the records cannot hold -- the
+  // host checks the caller's -- leaves them unwritten)
+  if (e > b && (PASS == 0 || (k != 0 && k <= 8u * RPK))) {
+    const uint64_t b0 = MODE == kKeyVar ? offs[b] : (uint64_t)b * stride;
+    const uint64_t b1 = MODE == kKeyVar ? offs[e] : (uint64_t)e * stride;
+    const uint64_t b_end = MODE == kKeyVar ? offs[n] : (uint64_t)n * stride;
+    const VarRsrc vr = var_rsrc(keys, b0, b1, b_end);
+    for (uint32_t i = b + tid; i < e; i += NT) {
+      uint32_t len;
+      const uint8_t* p = key_at<MODE>(keys, offs, stride, i, len);
+      if constexpr (PASS == 0) {
+        uint32_t none[1];
+        const uint32_t pt = (any_hash_bits<0>(keys, vr, p, len, nb, k, none) >> kTileShift) / q;
+        if (pt < n_parts) atomicAdd(s_part + pt, (uint32_t)RPK);
+      } else {
+        uint32_t bits[8 * RPK];
+        const uint32_t blk = any_hash_bits<8 * RPK>(keys, vr, p, len, nb, k, bits);
+        const uint32_t tg = blk >> kTileShift, pt = tg / q;
+        if (pt >= n_parts) continue;
+        rec_store_key<RPK>(out, atomicAdd(s_part + pt, (uint32_t)RPK), blk & (kTileBlocks - 1), tg - pt * q, bits);
+      }
+    }
+  }
+  if constexpr (PASS == 0) {
+    __syncthreads();
+    for (uint32_t t = tid; t < n_parts; t += NT) H[t] = s_part[t];
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1858,7 +1961,8 @@ __global__ __launch_bounds__(kPartThreads) void bloom_part_keys24(const tkv_amq_
   part_keys24(sg, a, s_part);
 }
 
-// routed items: 12-byte bit records for k <= 8, 16-byte keys above (tkv_amq_bloom_route)
+// routed items: 12-byte bit records (k <= 8; above, the wide records of a launch with 12-byte
+// regions), or with k > 8 and 16-byte regions the 16-byte keys (tkv_amq_bloom_route)
 __global__ __launch_bounds__(kPartThreads) void bloom_part_routed(const tkv_amq_segment* __restrict__ segs,
                                                                   PartArgs a)
 {
@@ -1866,18 +1970,19 @@ __global__ __launch_bounds__(kPartThreads) void bloom_part_routed(const tkv_amq_
   const tkv_amq_segment sg = segs[0];
   const uint32_t k = sg.hash_count;
   if (k == 0) return;
-  if (k <= 8) part_body<0, kSrcRec12>(sg, a, s_part);
+  if (k <= 8 || a.g.rb == 12) part_body<0, kSrcRec12>(sg, a, s_part);
   else part_body<0, kSrcRaw16>(sg, a, s_part);
 }
 
-// Keys of any other shape (variable-length through offsets, or a fixed stride; k <= 8) for the
-// tiled build: one thread per key hashes it into its 12-byte bit record, the tile in the
-// record's tile field (the filter has <= kDirectMaxTiles tiles), and the partition then sorts
+// Keys of any other shape (variable-length through offsets, or a fixed stride; k <= 16) for the
+// tiled build: one thread per key hashes it into its RPK 12-byte bit records (rpk * i and, a
+// wide record, rpk * i + 1), the tile in the record's tile field (the filter has <=
+// kDirectMaxTiles tiles), and the partition then sorts
 // the records (kSrcRec12) as it sorts routed ones.  A pass of its own, at full occupancy, hides
 // the latency of the keys' scattered byte loads, which the partition's batch loop could not
 // (round 6: hashing them inside the partition ran at 97.5 us for 3M variable-length keys).
 // (Round 5: such a leaf past the window path set its bits with device atomics, 3.6 Gkeys/s.)
-template <int MODE>
+template <int MODE, int RPK>
 __global__ __launch_bounds__(256) void bloom_any_records(const uint8_t* __restrict__ keys,
                                                          const uint64_t* __restrict__ offs, uint32_t stride,
                                                          const tkv_amq_segment* __restrict__ segs, uint32_t n,
@@ -1886,39 +1991,17 @@ __global__ __launch_bounds__(256) void bloom_any_records(const uint8_t* __restri
   const tkv_amq_segment sg = segs[0];
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   const uint32_t k = sg.hash_count;
-  if (i >= n || i >= sg.n_keys || k == 0 || k > 8) return;
-  // the leaf's bytes through a buffer resource: a key under 32 bytes as one 32-byte window
-  // (two 16-byte loads; KeyWin, as the VQF producers read them) instead of its lanes, tail
-  // word and tail bytes one load each
+  if (i >= n || i >= sg.n_keys || k == 0 || k > 8u * RPK) return;
+  // the leaf's bytes through a buffer resource
   const uint64_t n_all = min(n, sg.n_keys);
   const uint64_t b0 = MODE == kKeyVar ? offs[sg.key_begin] : sg.key_begin * stride;
   const uint64_t b1 = MODE == kKeyVar ? offs[sg.key_begin + n_all] : (sg.key_begin + n_all) * stride;
   const VarRsrc vr = var_rsrc(keys, b0, b1, b1);
   uint32_t len;
   const uint8_t* p = key_at<MODE>(keys, offs, stride, sg.key_begin + i, len);
-  uint32_t bits[8], r0, r1, r2;
-  uint32_t blk;
-  if (len < 32 && vr.nrec) {
-    KeyWin kw;
-    key_win_load(vr, (uint32_t)(p - keys - vr.base), kw);
-    uint64_t l[3];
-    uint32_t t4, tb;
-    key_win_parts(kw, len, l, t4, tb);
-    const XxhShort x(len, l, t4, tb);
-    const uint64_t h0 = x.finish(c_bloom.seed_p5[0]);
-    bits[0] = (uint32_t)h0 & 511u;
-#pragma unroll
-    for (uint32_t j = 1; j < 8; ++j) bits[j] = j < k ? x.finish_lo9(c_bloom.seed_p5[j]) & 511u : bits[0];
-    blk = (uint32_t)__umul64hi(h0, (uint64_t)sg.n_blocks);
-  } else {
-    blk = rec_hash_bits_any(KeyRef{p, len}, sg.n_blocks, k, bits);
-  }
-  rec_pack(blk & (kTileBlocks - 1), blk >> kTileShift, bits, r0, r1, r2);
-  uint3 v;
-  v.x = r0;
-  v.y = r1;
-  v.z = r2;
-  reinterpret_cast<uint3*>(recs)[i] = v;
+  uint32_t bits[8 * RPK];
+  const uint32_t blk = any_hash_bits<8 * RPK>(keys, vr, p, len, sg.n_blocks, k, bits);
+  rec_store_key<RPK>(recs, (uint64_t)RPK * i, blk & (kTileBlocks - 1), blk >> kTileShift, bits);
 }
 
 // The one-pass route (k <= 8): every key hashed once into its 12-byte bit record, counting-
@@ -1999,10 +2082,11 @@ __global__ __launch_bounds__(256) void bloom_route_ovf_apply(const tkv_amq_segme
   }
 }
 
-// the tile and overflow kernels' records are 16-byte keys when the partition had them
+// the tile and overflow kernels' records are 16-byte keys when the partition had them: k > 8
+// from 16-byte keys, in 16-byte regions (12-byte regions at k > 8 hold wide records)
 __device__ inline bool part_raw(const tkv_amq_segment& sg, const PartArgs& a)
 {
-  return sg.hash_count > 8 && a.kb != 24;
+  return sg.hash_count > 8 && a.kb != 24 && a.g.rb != 12;
 }
 
 template <int K>
@@ -2107,8 +2191,8 @@ __device__ __attribute__((always_inline)) inline void tile_run(const tkv_amq_seg
   __syncthreads();
   if (raw) tile_body<0, true>(sg, a, s_img, t, w_lo, w_hi);
   else if (k == 7) tile_body<7, false>(sg, a, s_img, t, w_lo, w_hi);
-  else if (k == 8) tile_body<8, false>(sg, a, s_img, t, w_lo, w_hi);
-  else tile_body<0, false>(sg, a, s_img, t, w_lo, w_hi);  // (k > 8 with 24-byte keys: eight bits)
+  else if (k >= 8) tile_body<8, false>(sg, a, s_img, t, w_lo, w_hi);  // (k > 8: every record's eight)
+  else tile_body<0, false>(sg, a, s_img, t, w_lo, w_hi);
   __syncthreads();
   uint8_t* payload = out + sg.out_offset;
   const bool hdr = t == 0 && sp == 0 && (a.tile0 == 0 || hdr_always);
@@ -4970,6 +5054,34 @@ inline void launch_route(const RouteGeom& g, hipStream_t s, const uint8_t* keys,
                        q, reinterpret_cast<uint4*>(out_keys), min_k);
 }
 
+// The route of n keys of any shape (offs: variable-length, else the fixed stride) into
+// g.n_parts parts of q tiles as rpk records per key, the part totals (in records) left where
+// launch_route leaves them.
+template <int MODE, int RPK>
+inline void launch_route_any_as(const RouteGeom& g, hipStream_t s, const uint8_t* keys, const uint64_t* offs,
+                                uint32_t stride, uint32_t n, const tkv_amq_segment* d_seg, uint32_t q,
+                                uint32_t* ws, uint32_t* out_recs)
+{
+  const size_t hl = 4ull * g.n_parts;
+  const dim3 grid(g.P), block(256);
+  hipLaunchKernelGGL((route_any<0, MODE, RPK, 256>), grid, block, hl, s, keys, offs, stride, d_seg, ws, g.n_parts,
+                     g.per, n, q, nullptr);
+  hipLaunchKernelGGL(route_scan_cols, dim3(g.n_parts), dim3(256), 0, s, ws, g.P, g.n_parts);
+  hipLaunchKernelGGL(route_scan_parts, dim3(1), dim3(256), 0, s, ws, g.P, g.n_parts);
+  hipLaunchKernelGGL((route_any<1, MODE, RPK, 256>), grid, block, hl, s, keys, offs, stride, d_seg, ws, g.n_parts,
+                     g.per, n, q, out_recs);
+}
+
+inline void launch_route_any(const RouteGeom& g, hipStream_t s, const uint8_t* keys, const uint64_t* offs,
+                             uint32_t stride, uint32_t n, const tkv_amq_segment* d_seg, uint32_t q, uint32_t rpk,
+                             uint32_t* ws, uint32_t* out_recs)
+{
+  if (offs && rpk == 2) launch_route_any_as<kKeyVar, 2>(g, s, keys, offs, 0u, n, d_seg, q, ws, out_recs);
+  else if (offs) launch_route_any_as<kKeyVar, 1>(g, s, keys, offs, 0u, n, d_seg, q, ws, out_recs);
+  else if (rpk == 2) launch_route_any_as<kKeyFixed, 2>(g, s, keys, nullptr, stride, n, d_seg, q, ws, out_recs);
+  else launch_route_any_as<kKeyFixed, 1>(g, s, keys, nullptr, stride, n, d_seg, q, ws, out_recs);
+}
+
 // Tiles per routed part (a filter past kDirectMaxTiles): the fewer tiles a partition spreads
 // a batch over, the longer each tile's run per store (fewer partial-line writes), until the
 // route's output over that many parts pays more than the part builds save; and at most one
@@ -5234,9 +5346,9 @@ inline uint32_t bloom_k_of(uint64_t n_keys, uint64_t n_blocks)
 }
 
 // One filter of keys of any other shape (variable-length, or a fixed stride other than 16 and
-// 24) with k <= 8 and at most kDirectMaxTiles tiles: the tiled build from bit records that
-// bloom_any_records hashes, tiles split over the chip below 128 of them.  Workspace: the
-// records, the partition's, the partial tile images.
+// 24) with k <= 16 and at most kDirectMaxTiles tiles: the tiled build from bit records that
+// bloom_any_records hashes (two per key above k = 8: wide records), tiles split over the chip
+// below 128 of them.  Workspace: the records, the partition's, the partial tile images.
 struct AnyPlan {
   PartGeom pg;
   uint32_t split;
@@ -5245,32 +5357,41 @@ struct AnyPlan {
 
 inline bool any_tiled_ok(uint32_t k, uint64_t n_keys, uint64_t n_blocks)
 {
-  return k >= 1 && k <= 8 && filter_tiles(n_blocks) <= kDirectMaxTiles && n_keys <= 0xffffffffull;
+  return bloom_rpk(k) != 0 && filter_tiles(n_blocks) <= kDirectMaxTiles && bloom_rpk(k) * n_keys <= 0xffffffffull;
 }
 
-inline AnyPlan any_plan(uint64_t n_keys, uint64_t n_blocks)
+// (k: any_tiled_ok's)
+inline AnyPlan any_plan(uint32_t k, uint64_t n_keys, uint64_t n_blocks)
 {
   AnyPlan p{};
   const uint32_t T = filter_tiles(n_blocks);
-  p.pg = part_geom(n_keys, n_keys, T, 12, mono_wg_items(n_keys, 32ull * kPartThreads));
+  const uint64_t n_recs = bloom_rpk(k) * n_keys;
+  p.pg = part_geom(n_recs, n_recs, T, 12, mono_wg_items(n_recs, 32ull * kPartThreads));
   p.split = tile_split(T);
-  p.part_off = align256(12ull * n_keys);
+  p.part_off = align256(12ull * n_recs);
   p.img_off = align256(p.part_off + p.pg.bytes);
   p.bytes = p.split > 1 ? p.img_off + (uint64_t)T * p.split * (64ull * kTileBlocks) : p.img_off;
   return p;
 }
 
 // keys [0, n) of segment 0 (from its key_begin), offs != nullptr: variable-length
-inline void launch_any(const AnyPlan& p, hipStream_t s, const uint8_t* keys, const uint64_t* offs, uint32_t stride,
-                       uint32_t n, const tkv_amq_segment* d_seg, uint8_t* ws, uint8_t* d_out)
+inline void launch_any(const AnyPlan& p, uint32_t k, hipStream_t s, const uint8_t* keys, const uint64_t* offs,
+                       uint32_t stride, uint32_t n, const tkv_amq_segment* d_seg, uint8_t* ws, uint8_t* d_out)
 {
   uint32_t* recs = reinterpret_cast<uint32_t*>(ws);
-  const uint32_t g = (uint32_t)div_up(n, 256);
+  const uint32_t g = (uint32_t)div_up(n, 256), rpk = bloom_rpk(k);
+  const dim3 grid(g), block(256);
   if (g) {
-    if (offs) hipLaunchKernelGGL(bloom_any_records<kKeyVar>, dim3(g), dim3(256), 0, s, keys, offs, 0u, d_seg, n, recs);
-    else hipLaunchKernelGGL(bloom_any_records<kKeyFixed>, dim3(g), dim3(256), 0, s, keys, offs, stride, d_seg, n, recs);
+    if (offs && rpk == 2)
+      hipLaunchKernelGGL((bloom_any_records<kKeyVar, 2>), grid, block, 0, s, keys, offs, 0u, d_seg, n, recs);
+    else if (offs)
+      hipLaunchKernelGGL((bloom_any_records<kKeyVar, 1>), grid, block, 0, s, keys, offs, 0u, d_seg, n, recs);
+    else if (rpk == 2)
+      hipLaunchKernelGGL((bloom_any_records<kKeyFixed, 2>), grid, block, 0, s, keys, offs, stride, d_seg, n, recs);
+    else
+      hipLaunchKernelGGL((bloom_any_records<kKeyFixed, 1>), grid, block, 0, s, keys, offs, stride, d_seg, n, recs);
   }
-  PartArgs a{reinterpret_cast<const uint8_t*>(recs), n, 0u, 0u, 16u, nullptr, 0u, ws + p.part_off, p.pg};
+  PartArgs a{reinterpret_cast<const uint8_t*>(recs), rpk * n, 0u, 0u, 16u, nullptr, 0u, ws + p.part_off, p.pg};
   a.split = p.split;
   a.part_img = ws + p.img_off;
   launch_part_build(kSrcRec12, a, s, d_seg, d_out, 0u);
@@ -5447,7 +5568,7 @@ inline uint64_t bloom_oversize_ws_bytes(const tkv_amq_segment* segs, uint32_t n_
       } else if (fixed) {
         big = std::max(big, mono_plan(g.n_keys, g.n_blocks).bytes);
       } else if (any_tiled_ok(g.hash_count, g.n_keys, g.n_blocks)) {
-        big = std::max(big, any_plan(g.n_keys, g.n_blocks).bytes);  // (bloom_part_any)
+        big = std::max(big, any_plan(g.hash_count, g.n_keys, g.n_blocks).bytes);  // (bloom_part_any)
       }
     }
     const uint64_t small = n_small ? bloom_batch_ws_bytes(n_small, small_keys, small_max) : 0;
@@ -5660,7 +5781,7 @@ int tkv_amq_plan(int kind, const uint64_t* counts, const uint64_t* src_ids, uint
       // (the plan does not know the key shape: other shapes take bloom_any_records' records)
       *ws_bytes = std::max<uint64_t>({mono_plan(key_begin, max_blocks).bytes, win_ws,
                                       any_tiled_ok(segs[0].hash_count, key_begin, max_blocks)
-                                          ? any_plan(key_begin, max_blocks).bytes
+                                          ? any_plan(segs[0].hash_count, key_begin, max_blocks).bytes
                                           : uint64_t{0}});
     else if (kind == TKV_AMQ_BLOOM)
       *ws_bytes = bloom_split_ws_bytes(n_segs, bloom_split_parts(n_segs, key_begin, max_blocks),
@@ -5832,7 +5953,7 @@ static int build_batch(int kind, const uint8_t* keys, const uint64_t* offs, uint
     }
     const bool mono_any = mono_part && !mono16 && !mono24 && mode != kKey16 && mono_mode != kKey24 &&
                           any_tiled_ok(k_route, sizing_keys, max_blocks) &&
-                          ws_bytes >= any_plan(sizing_keys, max_blocks).bytes;
+                          ws_bytes >= any_plan(k_route, sizing_keys, max_blocks).bytes;
     if (mono16 || mono24) {
       // one monolithic filter: every key hashed once into its bit record, records partitioned
       // by tile (routed into parts first beyond kDirectMaxTiles tiles), tiles built in LDS
@@ -5841,7 +5962,7 @@ static int build_batch(int kind, const uint8_t* keys, const uint64_t* offs, uint
     } else if (mono_any) {
       // one filter of variable-length or other fixed-size keys: the same, from bit records
       // (bloom_any_records)
-      launch_any(any_plan(sizing_keys, max_blocks), s, keys, mode == kKeyVar ? offs : nullptr, stride,
+      launch_any(any_plan(k_route, sizing_keys, max_blocks), k_route, s, keys, mode == kKeyVar ? offs : nullptr, stride,
                  (uint32_t)sizing_keys, d_segs, static_cast<uint8_t*>(d_ws), d_out);
     } else {
       // fewer than kBloomSpreadSegs leaves, leaves beyond the LDS budget in a multi-leaf batch,
@@ -6168,16 +6289,16 @@ int tkv_amq_build_ex(int kind, const uint8_t* keys, const uint64_t* offs, uint32
     const bool mono = rest_bytes >= mp.bytes &&
                       (mode == kKey16 || (bmode == kKey24 && (mp.g == 1 || (mp.blocks && k >= 1 && k <= 8))));
     const bool any = !mono && mode != kKey16 && bmode != kKey24 && any_tiled_ok(g.hash_count, g.n_keys, g.n_blocks) &&
-                     rest_bytes >= any_plan(g.n_keys, g.n_blocks).bytes;
+                     rest_bytes >= any_plan(g.hash_count, g.n_keys, g.n_blocks).bytes;
     if (mono) {
       launch_mono(mp, s, keys, mode == kKey16 ? 16u : 24u, g.n_keys, d_segs + i, rest, d_out, g.key_begin);
     } else if (any) {
       // variable-length or other fixed-size keys: hashed into bit records (bloom_any_records),
       // then the tiled build
-      launch_any(any_plan(g.n_keys, g.n_blocks), s, keys, mode == kKeyVar ? offs : nullptr, stride,
+      launch_any(any_plan(g.hash_count, g.n_keys, g.n_blocks), g.hash_count, s, keys, mode == kKeyVar ? offs : nullptr, stride,
                  (uint32_t)g.n_keys, d_segs + i, rest, d_out);
     } else {
-      // other key shapes (or no room): device atomics for this leaf alone
+      // other key shapes past k = 16 (or no room): device atomics for this leaf alone
       hipLaunchKernelGGL(bloom_global_init, dim3(1), dim3(256), 0, s, d_segs + i, d_out);
       const uint32_t g2 = (uint32_t)std::min<uint64_t>(div_up(g.n_keys, 256), 8192);
       if (g2) {
@@ -6276,6 +6397,40 @@ int tkv_amq_bloom_route_records_ex(const uint8_t* d_keys, uint32_t key_bytes, ui
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
 
+uint32_t tkv_amq_bloom_records_per_key(uint32_t hash_count) { return bloom_rpk(hash_count); }
+
+uint64_t tkv_amq_bloom_route_records_any_ws_bytes(uint64_t n_keys, uint32_t n_parts, uint32_t hash_count)
+{
+  if (bloom_rpk(hash_count) == 0) return 0;
+  return tkv_amq_bloom_route_ws_bytes(n_keys, n_parts);
+}
+
+int tkv_amq_bloom_route_records_any(const uint8_t* keys, const uint64_t* key_offsets, uint32_t key_stride,
+                                    uint64_t n_keys, const tkv_amq_segment* d_seg, uint32_t n_blocks,
+                                    uint32_t hash_count, uint32_t n_parts, uint8_t* d_recs12,
+                                    uint32_t* d_part_counts, void* d_ws, uint64_t ws_bytes, void* stream)
+{
+  if (tkv_amq_device_count() == 0) return TKV_AMQ_UNAVAILABLE;
+  const uint32_t rpk = bloom_rpk(hash_count);
+  if (rpk == 0 || n_parts == 0 || n_parts > kRouteMaxParts || n_blocks == 0 || !d_seg || !d_part_counts ||
+      n_keys > 0xffffffffull || rpk * n_keys > 0xffffffffull || (!key_offsets && key_stride == 0))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  const uint32_t q = (uint32_t)div_up(filter_tiles(n_blocks), n_parts);
+  if (q > kRecPartMaxTiles) return TKV_AMQ_INVALID_ARGUMENT;
+  if (n_keys && (!keys || !d_recs12 || (reinterpret_cast<uintptr_t>(d_recs12) & 3) ||
+                 (reinterpret_cast<uintptr_t>(key_offsets) & 7)))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  const RouteGeom g = route_geom(n_keys, n_parts);
+  if (!d_ws || (reinterpret_cast<uintptr_t>(d_ws) & 3) || ws_bytes < g.bytes) return TKV_AMQ_INVALID_ARGUMENT;
+  const hipStream_t s = as_stream(stream);
+  uint32_t* w = static_cast<uint32_t*>(d_ws);
+  launch_route_any(g, s, keys, n_keys ? key_offsets : nullptr, key_stride, (uint32_t)n_keys, d_seg, q, rpk, w,
+                   reinterpret_cast<uint32_t*>(d_recs12));
+  if (hipMemcpyAsync(d_part_counts, w + g.h_words, 4ull * n_parts, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return TKV_AMQ_INTERNAL;
+  return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
+}
+
 uint64_t tkv_amq_bloom_build_range_records_ws_bytes(uint64_t n_recs, uint32_t tile_begin, uint32_t tile_end)
 {
   if (tile_end <= tile_begin || tile_end - tile_begin > kRecPartMaxTiles || n_recs > 0xffffffffull) return 0;
@@ -6290,8 +6445,7 @@ int tkv_amq_bloom_build_range_records(const uint8_t* d_recs12, uint64_t n_recs, 
   if (tkv_amq_device_count() == 0) return TKV_AMQ_UNAVAILABLE;
   const uint32_t T = filter_tiles(n_blocks);
   if (!d_seg || !d_out || n_blocks == 0 || tile_begin > tile_end || tile_end > T ||
-      tile_end - tile_begin > kRecPartMaxTiles || n_recs > 0xffffffffull || hash_count == 0 ||
-      hash_count > 8)
+      tile_end - tile_begin > kRecPartMaxTiles || n_recs > 0xffffffffull || bloom_rpk(hash_count) == 0)
     return TKV_AMQ_INVALID_ARGUMENT;
   if (n_recs && (!d_recs12 || (reinterpret_cast<uintptr_t>(d_recs12) & 3))) return TKV_AMQ_INVALID_ARGUMENT;
   if (tile_begin == tile_end) {

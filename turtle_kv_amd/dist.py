@@ -182,7 +182,8 @@ class PipelinedLeafGather:
 # 800 MiB of filter per rank).  Steps per build, the same at every world size:
 #   route     reorder the rank's keys by part (tkv_amq_bloom_route_records hashes each key once
 #             and ships its 12-byte bit record, k <= 8; tkv_amq_bloom_route ships the 16-byte
-#             key otherwise);
+#             key at k > 8; keys of any other shape leave as one record, or at 9 <= k <= 16 the
+#             two of a wide record, tkv_amq_bloom_route_records_any);
 #   exchange  one all-to-all of them (RCCL over xGMI; at world size 1 a local copy);
 #   build     each owned part built from its records (tkv_amq_bloom_build_range_records /
 #             _build_range), part after part;
@@ -214,6 +215,18 @@ def hash_shard_plan(n_blocks: int, world: int, records: bool = True) -> tuple[in
     return T, g, q
 
 
+def _key_form(keys):
+    """(data, offsets or None, stride, n) of a 2-D uint8 tensor or a KeyBatch."""
+    from .filters import KeyBatch
+    if isinstance(keys, KeyBatch):
+        return keys.data, keys.offsets, int(keys.stride), int(keys.n)
+    if keys.dim() != 2:
+        from . import abi
+        raise abi.TkvAmqError(abi.INVALID_ARGUMENT, "hash-range sharding takes [n, width] uint8 keys or a "
+                              f"KeyBatch, got shape {tuple(keys.shape)}")
+    return keys, None, int(keys.shape[1]), int(keys.shape[0])
+
+
 def hash_shard_tiles(n_blocks: int, world: int) -> tuple[int, int]:
     """(T, q): the filter's tiles and the tiles per part when each of `world` parts is one
     range build (the ABI's tkv_amq_bloom_route with n_parts = world)."""
@@ -228,7 +241,14 @@ class ExactHashShardedBloom:
     whole filter payload (header + bitmap, byte-identical to a one-GPU tkv_amq_build of the
     concatenated keys) on every rank.  HashShardedBloom uses it for k > 8 (16-byte keys travel)
     and when a pipelined step lost overflow entries (keys far from uniform).  Buffers are
-    allocated once and grown when a rank receives more keys than before."""
+    allocated once and grown when a rank receives more keys than before.
+
+    Keys are a 2-D uint8 tensor of any width or a KeyBatch (fixed or variable-length).  What
+    travels is chosen per build from the key shape: [n, 16] at k > 8 the 16-byte keys; [n, 16]
+    or [n, 24] at k <= 8 one bit record per key; every other shape up to k = 16 (23 bits/key)
+    its bit records, two per key above k = 8 (tkv_amq_bloom_route_records_any; counts are in
+    records); other shapes at k > 16 are refused.  All ranks of one build must pass the same
+    key shape (the ranks exchange one kind of unit).  (T, g, q) do not depend on it."""
 
     def __init__(self, n_total_keys: int, bits_per_key: int, world: int, rank: int, device,
                  src_page_id: int = 0, group=None):
@@ -260,6 +280,8 @@ class ExactHashShardedBloom:
         self.d_seg = self.plan.device_segs(self.dev)
         self.counts = torch.zeros(self.n_parts, dtype=torch.int32, device=self.dev)
         self._bufs = {}
+        # what the last route() shipped: bit records (12 bytes) or 16-byte keys
+        self.route_records, self.route_unit = self.records, self.unit
 
     def _buf(self, name, nbytes):
         import torch
@@ -275,35 +297,50 @@ class ExactHashShardedBloom:
         return b, min(self.tile_end, b + self.q)
 
     def route(self, keys):
-        """keys [n, 16] (or [n, 24] with bit records) uint8 on the device -> (routed [n, unit],
-        per-part counts [n_parts], int64 on the device)."""
+        """keys (a 2-D uint8 tensor or a KeyBatch on the device) -> (routed [m, unit], per-part
+        counts [n_parts], int64 on the device), in the units the key shape travels as (the
+        class docstring; `route_records`, `route_unit`): m = n keys, or the keys' records."""
         import torch
         from . import abi
         from .filters import _ptr, _stream_handle
         L = abi.lib()
-        kb = keys.shape[1] if keys.dim() == 2 else 0
-        if not (kb == 16 or (kb == 24 and self.records)):
-            # bit records (k <= 8) are routed from 16- or 24-byte keys
-            # (tkv_amq_bloom_route_records_ex); keys themselves (k > 8) travel as 16 bytes only
-            # (tkv_amq_bloom_route / _build_range; INTEGRATION.md key shapes)
-            raise abi.TkvAmqError(abi.INVALID_ARGUMENT, "hash-range sharding takes [n, 16] uint8 "
-                                  "keys, or [n, 24] at <= 12 bits/key, got shape "
-                                  f"{tuple(keys.shape)}")
-        n = keys.shape[0]
-        u = self.unit
-        routed = self._buf("routed", u * n)[:u * n].view(n, u)
+        data, offs, kb, n = _key_form(keys)
+        if not data.is_cuda:  # (the library reads them on the GPU)
+            raise abi.TkvAmqError(abi.INVALID_ARGUMENT, "hash-range sharding routes keys on the device, "
+                                  f"got shape {tuple(data.shape)} on {data.device}")
+        fixed = offs is None
         P = self.n_parts
-        if self.records:
+        if fixed and kb == 16 and not self.records:
+            # 16-byte keys at k > 8 travel as themselves (smaller than their two records)
+            self.route_records, self.route_unit = False, 16
+            routed = self._buf("routed", 16 * n)[:16 * n].view(n, 16)
+            ws = self._buf("route_ws", int(L.tkv_amq_bloom_route_ws_bytes(n, P)))
+            abi.check(L.tkv_amq_bloom_route(_ptr(data), n, _ptr(self.d_seg), self.n_blocks, P,
+                                            _ptr(routed), _ptr(self.counts), _ptr(ws), ws.numel(),
+                                            _stream_handle()), "tkv_amq_bloom_route")
+        elif fixed and kb in (16, 24) and self.records:
+            self.route_records, self.route_unit = True, 12
+            routed = self._buf("routed", 12 * n)[:12 * n].view(n, 12)
             ws = self._buf("route_ws", int(L.tkv_amq_bloom_route_records_ws_bytes(n, P)))
-            abi.check(L.tkv_amq_bloom_route_records_ex(_ptr(keys), kb, n, _ptr(self.d_seg), self.n_blocks,
+            abi.check(L.tkv_amq_bloom_route_records_ex(_ptr(data), kb, n, _ptr(self.d_seg), self.n_blocks,
                                                        self.hash_count, P, _ptr(routed),
                                                        _ptr(self.counts), _ptr(ws), ws.numel(),
                                                        _stream_handle()), "tkv_amq_bloom_route_records_ex")
         else:
-            ws = self._buf("route_ws", int(L.tkv_amq_bloom_route_ws_bytes(n, P)))
-            abi.check(L.tkv_amq_bloom_route(_ptr(keys), n, _ptr(self.d_seg), self.n_blocks, P,
-                                            _ptr(routed), _ptr(self.counts), _ptr(ws), ws.numel(),
-                                            _stream_handle()), "tkv_amq_bloom_route")
+            rpk = int(L.tkv_amq_bloom_records_per_key(self.hash_count))
+            if rpk == 0:
+                # a wide record holds 16 bit indices; past them only 16-byte keys travel
+                raise abi.TkvAmqError(abi.INVALID_ARGUMENT, "hash-range sharding above 23 bits/key "
+                                      f"(k = {self.hash_count} > 16) takes [n, 16] uint8 keys only, got "
+                                      + ("variable-length keys" if not fixed else f"{kb}-byte keys"))
+            self.route_records, self.route_unit = True, 12
+            m = rpk * n
+            routed = self._buf("routed", 12 * m)[:12 * m].view(m, 12)
+            ws = self._buf("route_ws", int(L.tkv_amq_bloom_route_records_any_ws_bytes(n, P, self.hash_count)))
+            abi.check(L.tkv_amq_bloom_route_records_any(_ptr(data) if n else None, _ptr(offs), 0 if offs is not None else kb,
+                                                        n, _ptr(self.d_seg), self.n_blocks, self.hash_count, P,
+                                                        _ptr(routed), _ptr(self.counts), _ptr(ws), ws.numel(),
+                                                        _stream_handle()), "tkv_amq_bloom_route_records_any")
         return routed, self.counts.to(dtype=torch.int64)
 
     def exchange(self, routed, part_counts):
@@ -312,7 +349,7 @@ class ExactHashShardedBloom:
         by part, and how many each sender sent for each of this rank's parts."""
         import torch
         import torch.distributed as dist
-        u, W, g = self.unit, self.world, self.g
+        u, W, g = self.route_unit, self.world, self.g
         gloo = dist.get_backend(self.group) != "nccl"
         pc = part_counts.cpu() if gloo else part_counts
         sub = torch.empty_like(pc)
@@ -385,7 +422,7 @@ class ExactHashShardedBloom:
 
     def _build_part(self, units, j):
         t0, t1 = self.part_tiles(j)
-        if self.records:
+        if self.route_records:
             self.build_range_records(units, t0, t1)
         else:
             self.build_range(units, t0, t1)
@@ -418,8 +455,9 @@ class ExactHashShardedBloom:
         """route + exchange + part builds: after it, this rank's byte range of the bitmap is
         final."""
         if not self._collective:
-            if keys.dim() == 2 and keys.shape[1] == 16 and self.T <= KEY_RANGE_MAX_TILES:
-                self.build_range(keys, 0, self.T)  # the partition makes the records itself
+            data, offs, kb, _ = _key_form(keys)
+            if offs is None and kb == 16 and self.T <= KEY_RANGE_MAX_TILES:
+                self.build_range(data, 0, self.T)  # the partition makes the records itself
                 return
             routed, pc = self.route(keys)  # (checks the key shape)
             self.build_owned(routed, pc.cpu().view(1, self.g))
@@ -467,8 +505,10 @@ class HashShardedBloom:
     partition hashes the keys itself; `direct=False` keeps the route), and a larger one's route
     writes the part builds' input directly.  k > 8 (bits_per_key >= 13), a rank holding
     more keys than the plan's chunks take, and a step whose blocks lost overflow entries (`lost()`;
-    keys far from uniform, e.g. one key repeated) go through ExactHashShardedBloom.  The receive
-    buffer holds round j's blocks at [j][chunk][sender]."""
+    keys far from uniform, e.g. one key repeated) go through ExactHashShardedBloom, as does a
+    `build` of keys the pipelined route does not take (not [n, 16] or [n, 24]: another width, or a
+    KeyBatch; `last_fallback` "key_shape"; every rank of a build passes the same shape).  The
+    receive buffer holds round j's blocks at [j][chunk][sender]."""
 
     def __init__(self, n_total_keys: int, bits_per_key: int, world: int, rank: int, device,
                  src_page_id: int = 0, group=None, chunks: int = 1, max_keys_per_rank=None,
@@ -490,6 +530,7 @@ class HashShardedBloom:
         self._exact = None
         self._exact_out = None
         self._fallback_out = None
+        self._shape_exact = None  # the exact builder of key shapes the pipelined route refuses
         self.last_fallback = None
         if not self.records:
             self._exact = ExactHashShardedBloom(n_total_keys, bits_per_key, world, rank, device,
@@ -820,6 +861,15 @@ class HashShardedBloom:
             self.step(keys, gather=True)
             return self._exact_out.clone()
         self.last_fallback = None
+        from .filters import KeyBatch
+        if isinstance(keys, KeyBatch) or keys.dim() != 2 or keys.shape[1] not in (16, 24):
+            # (a builder of its own: the next build of 16- or 24-byte keys is pipelined again)
+            self.last_fallback = "key_shape"
+            if self._shape_exact is None:
+                self._shape_exact = ExactHashShardedBloom(self.n_total_keys, self.bpk, self.world, self.rank,
+                                                          self.dev, self.src_page_id, self.group)
+            self._fallback_out = self._shape_exact.build(keys)
+            return self.filter().clone()
         if self._any_rank(keys.shape[0] > self.capacity):
             self.last_fallback = "keys_over_capacity"
         else:
