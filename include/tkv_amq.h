@@ -40,6 +40,10 @@
  *                           the same probes with KeyQuery::reject_page's page-id check
  *                           (tree/key_query.hpp:205-212,227-232) and KeyQuery::Metrics counters
  *                           (:36-60, updated at :154,157,210,231,243 and key_query.cpp:41,77)
+ *   tkv_amq_path_probe      a batch of point lookups' walks over their segments (tree/algo/
+ *                           nodes.hpp:158-187, segmented_levels.hpp:358-369): each key hashed
+ *                           once, reject_page asked of every filter on its path, the leaves
+ *                           still to search returned per query, in order
  *   tkv_amq_stage_keys      the EditView key range build_filter_for_leaf_in_job iterates
  *                           (core/merge_compactor.hpp:107-139) gathered into one contiguous
  *                           host key buffer for the H2D copy (host only)
@@ -434,6 +438,43 @@ int tkv_amq_bloom_probe_hashed_ex(const uint8_t* d_filters, const tkv_amq_segmen
                                   const uint32_t* d_pair_query, uint64_t n_pairs,
                                   const uint32_t* d_pair_leaf, uint8_t* d_result,
                                   const tkv_amq_probe_opts* opts, void* stream);
+
+/* Path probe: a batched multi-get's filter walk in one call (tree/algo/nodes.hpp:158-187,
+ * tree/algo/segmented_levels.hpp:358-369, tree/key_query.cpp:27-80).  Query i carries the
+ * ordered list of leaves its lookup would visit, in CSR form: entries
+ * [d_path_begin[i], d_path_begin[i+1]) of d_path_leaf (segment indices, newest level first).
+ * Each key is hashed once, in registers; every entry answers exactly as tkv_amq_probe /
+ * tkv_amq_*_probe_hashed[_ex] answer the pair (query i, that leaf): 0 = the filter rejects,
+ * 1 = maybe or cannot reject (leaf >= n_segs, a segment without a filter, a d_query_page_id
+ * mismatch, a VQF hash dropped by hash_val_shift).  The entries that answered 1 are query i's
+ * candidates -- the leaves still to search -- written in path order:
+ *   d_cand_leaf[d_cand_begin[i] .. d_cand_begin[i+1])   the leaves
+ *   d_cand_entry[same positions]                         their entry indices (if not NULL)
+ * d_cand_begin[0] == 0 and d_cand_begin[n_queries] is the total; nothing past the total is
+ * written (capacity n_entries).  The output is a function of the inputs only.
+ *  queries / query_offsets / query_stride   the key forms of tkv_amq_probe
+ *  d_entry_result   [n_entries] or NULL: the answer of every entry
+ *  opts             NULL, or fields indexed by ENTRY (as the hashed _ex probes index by pair);
+ *                   one count per entry, classified as there
+ *  d_workspace      tkv_amq_path_probe_ws_bytes(n_queries, n_entries) bytes, 16-byte aligned
+ * Both ends of a path are clamped to n_entries and end < begin reads as empty, so a malformed
+ * list gives a defined answer and never an out-of-range access.  If the clamped paths of a
+ * path_begin that is not monotone share entries, each query's candidates are still its own;
+ * d_entry_result at a shared entry holds the answer of one of the queries that cover it, and
+ * candidates that would not fit the capacity are dropped (the offsets stop at n_entries).
+ * Asynchronous on `stream`; never allocates, copies synchronously or synchronises.
+ * InvalidArgument: unknown kind, n_queries or n_entries above 0xffffffff, a null required
+ * buffer with a non-zero count, fixed keys with stride 0, a short or misaligned workspace.
+ * n_queries == 0 is OK and writes d_cand_begin[0] = 0.
+ * tkv_amq_path_probe_ws_bytes is a host function (no device needed): at least 16, and 0 for
+ * counts the probe refuses. */
+uint64_t tkv_amq_path_probe_ws_bytes(uint64_t n_queries, uint64_t n_entries);
+int tkv_amq_path_probe(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs, uint32_t n_segs,
+                       const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
+                       uint64_t n_queries, const uint32_t* d_path_begin, const uint32_t* d_path_leaf,
+                       uint64_t n_entries, uint8_t* d_entry_result, uint32_t* d_cand_begin,
+                       uint32_t* d_cand_leaf, uint32_t* d_cand_entry, const tkv_amq_probe_opts* opts,
+                       void* d_workspace, uint64_t workspace_bytes, void* stream);
 
 /* Key staging, host only (no device needed): the H2D front end.  The reference passes the
  * build a flattened range of EditView whose keys are KeyView = std::string_view into leaf /

@@ -1100,6 +1100,71 @@ class KeyQuery
     return OkStatus();
   }
 
+  // The batch form of a point lookup's walk (tree/algo/nodes.hpp:158-187,
+  // tree/algo/segmented_levels.hpp:358-369, key_query.cpp:27-80): key i would visit the leaves
+  // path_leaf[path_begin[i] .. path_begin[i+1]) -- indices into `segs`, newest level first --
+  // and reject_page is asked of each.  Every key is hashed once (tkv_amq_path_probe).
+  //  d_filters, d_segs, segs   the device filter array with its device and host segments, as a
+  //                            FilterBatchBuilder leaves them (device_segments(), segments())
+  //  cand_begin, cand_leaf     (out) key i's leaves still to search, in path order:
+  //                            cand_leaf[cand_begin[i] .. cand_begin[i+1])
+  //  truth                     optional, one per ENTRY (1 = the key is in that leaf)
+  // Counts one filter query per entry in metrics(), classified as reject_page classifies it.
+  Status candidate_leaves(FilterKind kind, const u8* d_filters, const tkv_amq_segment* d_segs,
+                          const std::vector<tkv_amq_segment>& segs, const std::vector<u32>& path_begin,
+                          const std::vector<u32>& path_leaf, std::vector<u32>& cand_begin,
+                          std::vector<u32>& cand_leaf, const std::vector<u8>* truth = nullptr)
+  {
+    const u64 n = keys_.size(), n_entries = path_leaf.size();
+    cand_begin.assign(n + 1, 0);
+    cand_leaf.clear();
+    if (tkv_amq_device_count() == 0) return Status::from(TKV_AMQ_UNAVAILABLE, "no HIP device");
+    if (path_begin.size() != n + 1 || (truth && truth->size() != n_entries))
+      return Status::from(TKV_AMQ_INVALID_ARGUMENT, "path lists");
+    if (n == 0) return OkStatus();
+    const u64 ws_bytes = tkv_amq_path_probe_ws_bytes(n, n_entries);
+    if (ws_bytes == 0) return Status::from(TKV_AMQ_INVALID_ARGUMENT, "path lists");
+    DeviceBuffer d_keys, d_offs, d_begin, d_leaf, d_cbegin, d_cleaf, d_truth, d_metrics, d_ws;
+    if (!d_begin.resize(4 * (n + 1)) || !d_leaf.resize(4 * n_entries) || !d_cbegin.resize(4 * (n + 1)) ||
+        !d_cleaf.resize(4 * n_entries) || !d_metrics.resize(sizeof(tkv_amq_probe_metrics)) ||
+        !d_ws.resize(ws_bytes) || (truth && !d_truth.resize(n_entries)))
+      return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+    bool fixed = false;
+    u32 stride = 16;
+    TKV_AMQ_REQUIRE_OK(detail::stage_keys(keys_, d_keys, d_offs, fixed, stride));
+    if (hipMemcpy(d_begin.get(), path_begin.data(), 4 * (n + 1), hipMemcpyHostToDevice) != hipSuccess ||
+        (n_entries && hipMemcpy(d_leaf.get(), path_leaf.data(), 4 * n_entries, hipMemcpyHostToDevice) != hipSuccess) ||
+        (truth && n_entries &&
+         hipMemcpy(d_truth.get(), truth->data(), n_entries, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemset(d_metrics.get(), 0, sizeof(tkv_amq_probe_metrics)) != hipSuccess)
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy path lists");
+    const tkv_amq_probe_opts opts{nullptr, truth ? d_truth.get() : nullptr,
+                                  d_metrics.get<tkv_amq_probe_metrics>()};
+    const int st = tkv_amq_path_probe((int)kind, d_filters, d_segs, (u32)segs.size(), d_keys.get(),
+                                      fixed ? nullptr : d_offs.get<u64>(), fixed ? stride : 0, n,
+                                      d_begin.get<u32>(), d_leaf.get<u32>(), n_entries, nullptr,
+                                      d_cbegin.get<u32>(), d_cleaf.get<u32>(), nullptr, &opts, d_ws.get(),
+                                      ws_bytes, nullptr);
+    if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_path_probe");
+    tkv_amq_probe_metrics pm{};
+    // (blocking copies on the null stream: they wait for the probe)
+    if (hipMemcpy(cand_begin.data(), d_cbegin.get(), 4 * (n + 1), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&pm, d_metrics.get(), sizeof(pm), hipMemcpyDeviceToHost) != hipSuccess)
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy candidates");
+    cand_leaf.resize(cand_begin[n]);
+    if (!cand_leaf.empty() &&
+        hipMemcpy(cand_leaf.data(), d_cleaf.get(), 4 * cand_leaf.size(), hipMemcpyDeviceToHost) != hipSuccess)
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy candidates");
+    Metrics& m = metrics();
+    m.total_filter_query_count.add(pm.total_filter_query_count);
+    m.no_filter_page_count.add(pm.no_filter_page_count);
+    m.page_id_mismatch_count.add(pm.page_id_mismatch_count);
+    m.filter_reject_count.add(pm.filter_reject_count);
+    m.filter_positive_count.add(pm.filter_positive_count);
+    if (truth) m.filter_false_positive_count.add(pm.filter_false_positive_count);
+    return OkStatus();
+  }
+
  private:
   std::vector<std::string_view> keys_;
 };

@@ -11,7 +11,8 @@ from .filters import (BoolStatus, FilterPage, FilterPlan, KeyBatch, KeyQuery, Pa
                       vqf_nslots_for_size, vqf_probe_hashed, vqf_required_size, key_views,
                       stage_keys, BloomFilterMetrics, QuotientFilterMetrics,
                       plan_filter_stats, record_filter_metrics, TreeOptions, plan_filter_pages,
-                      page_header_fields, ProbeMetrics, KeyQueryMetrics)
+                      page_header_fields, ProbeMetrics, KeyQueryMetrics, probe_paths,
+                      PathProbeResult, path_probe_workspace_bytes)
 
 __all__ = [
     "abi", "BLOOM", "VQF", "TkvAmqError", "BoolStatus", "FilterPage", "FilterPlan", "KeyBatch",
@@ -22,4 +23,5 @@ __all__ = [
     "bloom_probe_hashed", "HostFilterPipeline", "key_views", "stage_keys",
     "BloomFilterMetrics", "QuotientFilterMetrics", "plan_filter_stats", "record_filter_metrics",
     "TreeOptions", "plan_filter_pages", "page_header_fields", "ProbeMetrics", "KeyQueryMetrics",
+    "probe_paths", "PathProbeResult", "path_probe_workspace_bytes",
 ]

@@ -93,6 +93,7 @@ EXPORTS = [
     "tkv_amq_bloom_blocks_lost", "tkv_amq_build_ex",
     "tkv_amq_bloom_records_per_key", "tkv_amq_bloom_route_records_any_ws_bytes",
     "tkv_amq_bloom_route_records_any",
+    "tkv_amq_path_probe_ws_bytes", "tkv_amq_path_probe",
 ]
 
 
@@ -199,6 +200,12 @@ def lib(build_if_missing: bool = True):
     L.tkv_amq_vqf_probe_hashed_ex.argtypes = [vp, vp, u32, vp, vp, u64, vp, vp, popts, vp]
     L.tkv_amq_bloom_probe_hashed_ex.restype = i32
     L.tkv_amq_bloom_probe_hashed_ex.argtypes = [vp, vp, u32, vp, u32, vp, u64, vp, vp, popts, vp]
+    if hasattr(L, "tkv_amq_path_probe"):
+        L.tkv_amq_path_probe_ws_bytes.restype = u64
+        L.tkv_amq_path_probe_ws_bytes.argtypes = [u64, u64]
+        L.tkv_amq_path_probe.restype = i32
+        L.tkv_amq_path_probe.argtypes = [i32, vp, vp, u32, vp, vp, u32, u64, vp, vp, u64, vp, vp, vp,
+                                         vp, popts, vp, u64, vp]
     if hasattr(L, "tkv_amq_bloom_route"):
         L.tkv_amq_bloom_route_ws_bytes.restype = u64
         L.tkv_amq_bloom_route_ws_bytes.argtypes = [u64, u32]

@@ -4748,6 +4748,384 @@ __global__ __launch_bounds__(256) void vqf_hash_kernel(const uint8_t* __restrict
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Path probe (tkv_amq_path_probe): one lane per query walks its CSR list of leaves
+// ---------------------------------------------------------------------------------------
+// Three launches, no atomics on an output position:
+//   path_probe_kernel   lane i hashes query i once (the seed-independent rounds stay in
+//                       registers), tests the filter of every entry of its path, keeps the
+//                       answers of its first kPathMaskEntries entries as a bit mask (later
+//                       entries only as bytes), and counts its candidates; the workgroup scans
+//                       its 256 counts (path_block_scan256): cand_begin[i] <- prefix inside the workgroup,
+//                       wg_total[w] <- the workgroup's sum
+//   path_scan_totals    one workgroup: exclusive scan of wg_total in passes of kPathScanSpan
+//   path_scatter        lane i again: cand_begin[i] += wg_total[w], then its candidates in path
+//                       order from the mask (answer bytes past kPathMaskEntries)
+// The mask is the query's own, so two paths that share entries (possible only when path_begin
+// is not monotone) cannot disturb each other's candidates.
+constexpr uint32_t kPathScanPerThread = 4;
+constexpr uint32_t kPathScanSpan = 256 * kPathScanPerThread;  // workgroup totals per scan pass
+constexpr uint32_t kPathMaskEntries = 32;
+
+// exclusive scan of 256 per-thread values: a shuffle scan inside each wave, the four wave sums
+// through LDS (two barriers, where block_exclusive_scan256 takes eighteen); s_w: 4 words
+__device__ inline uint32_t path_block_scan256(uint32_t v, uint32_t* s_w, uint32_t* total)
+{
+  const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t u = __shfl_up(inc, d, 64);
+    if (lane >= (uint32_t)d) inc += u;
+  }
+  if (lane == 63) s_w[wave] = inc;
+  __syncthreads();
+  const uint32_t w0 = s_w[0], w1 = s_w[1], w2 = s_w[2], w3 = s_w[3];
+  __syncthreads();  // (s_w is written again by the caller's next pass)
+  *total = w0 + w1 + w2 + w3;
+  const uint32_t wave_base = (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u);
+  return wave_base + inc - v;
+}
+
+struct PathArgs {
+  const uint8_t* filters;
+  const tkv_amq_segment* segs;
+  uint32_t n_segs;
+  const uint8_t* q;
+  const uint64_t* qoffs;
+  uint32_t stride;
+  uint32_t n_queries;
+  const uint32_t* path_begin;
+  const uint32_t* path_leaf;
+  uint32_t n_entries;
+  uint32_t every_answer;  // 1: `answers` is the caller's d_entry_result, every entry is written
+  uint8_t* answers;       // d_entry_result, or the workspace's bytes for entries past the mask
+  uint32_t* mask;         // workspace: [n_queries]
+  uint32_t* wg_total;     // workspace: [n_wgs]
+  uint32_t* cand_begin;
+  uint32_t* cand_leaf;
+  uint32_t* cand_entry;
+  uint32_t n_wgs;
+};
+
+// entries [b, e) of query i: both ends clamped to n_entries, end < begin reads as empty
+__device__ inline void path_range(const PathArgs& a, uint64_t i, uint32_t& b, uint32_t& e)
+{
+  b = min(a.path_begin[i], a.n_entries);
+  e = min(a.path_begin[i + 1], a.n_entries);
+  if (e < b) e = b;
+}
+
+// one lane's walk: its answers so far
+struct PathWalk {
+  uint32_t mask = 0;
+  uint32_t cnt = 0;
+  template <bool kOpts>
+  __device__ inline void record(const PathArgs& a, const tkv_amq_probe_opts& opts, ProbeTally& t,
+                                uint32_t r, uint32_t j, uint32_t ent)
+  {
+    const uint32_t bit = r & 1u;
+    if (j < kPathMaskEntries) mask |= bit << j;
+    if (a.every_answer || j >= kPathMaskEntries) a.answers[ent] = (uint8_t)bit;
+    cnt += bit;
+    if constexpr (kOpts) t.add(r, opts.d_truth, ent);
+  }
+};
+
+// A 16-byte key's Bloom test in two halves, so that the next entry's descriptor (and, with
+// options, its filter's page id) is in flight while this entry's block is loaded and tested:
+// fetch = descriptor, class, block address; test = the block's loads and bit tests.
+// (Measured on 200M entries: 4.49 ms with the descriptor fetched ahead, 4.66 without, at the
+// same 66 VGPRs.  Loading the next block ahead as well held two blocks in registers: 108
+// VGPRs, 4 waves.)
+struct BloomEntry16 {
+  const uint4* blk;
+  uint32_t k_cls;  // hash_count | class << 16
+  __device__ inline uint32_t k() const { return k_cls & 0xffffu; }
+  __device__ inline uint32_t cls() const { return k_cls >> 16; }
+};
+
+template <bool kOpts>
+__device__ inline BloomEntry16 bloom_entry16_fetch(const uint8_t* __restrict__ filters,
+                                                   const tkv_amq_segment* __restrict__ segs,
+                                                   uint32_t n_segs, uint32_t leaf, uint64_t h0,
+                                                   const uint64_t* page_ids, uint32_t ent)
+{
+  BloomEntry16 f;
+  const ProbeDesc d = load_probe_desc(segs, leaf, n_segs);
+  uint32_t cls = d.hash_count == 0 ? kNoFilter : kChecked;
+  if constexpr (kOpts) {
+    if (cls == kChecked && !page_id_matches(filters + d.out_offset, 16, page_ids, ent)) cls = kIdMismatch;
+  }
+  f.k_cls = d.hash_count | (cls << 16);
+  f.blk = reinterpret_cast<const uint4*>(filters + d.out_offset + kBloomHeader +
+                                         64 * __umul64hi(h0, (uint64_t)d.n_blocks));
+  return f;
+}
+
+// Bit indices 1..7 of a 16-byte key (what hash_count <= 8 needs, i.e. up to 12 bits per key),
+// finished once per query and packed 9 bits each into three registers; a filter with more
+// hashes finishes indices 8.. again from the shared lane rounds (finish_lo9), per entry.
+struct BloomBits16 {
+  uint32_t w[3];
+  __device__ inline explicit BloomBits16(const Xxh16& x)
+  {
+    w[0] = w[1] = w[2] = 0;
+#pragma unroll
+    for (int j = 1; j < 8; ++j)
+      w[(j - 1) / 3] |= (x.finish_lo9(c_bloom.rhinit16[j]) & 511u) << (9 * ((j - 1) % 3));
+  }
+  // `zero` is 0 at run time, but comes from the entry, so that the unpacking stays in the loop
+  // over the path: hoisted out of it, every index is held as an LDS address and a shift, two
+  // registers each, and the kernel drops to 6 waves per SIMD
+  template <int J>
+  __device__ inline uint32_t get(uint32_t zero) const
+  {
+    return (w[(J - 1) / 3] >> (9 * ((J - 1) % 3) + zero)) & 511u;
+  }
+};
+
+template <int J>
+__device__ inline uint32_t bloom_bits16_and(const BloomBits16& bits, const uint32_t* slot32, uint32_t k,
+                                            uint32_t zero, uint32_t ok)
+{
+  if constexpr (J < 8) {
+    const uint32_t bit = bits.get<J>(zero);
+    const uint32_t v = slot32[bit >> 5] >> (bit & 31);
+    return bloom_bits16_and<J + 1>(bits, slot32, k, zero, ok & ((uint32_t)J < k ? v : 1u));
+  } else {
+    return ok;
+  }
+}
+
+// the block test of probe_block16 (four 16-byte loads staged in the lane's LDS slot, the bit
+// tests LDS reads) with the cached indices.  The hash state a filter of more than 8 hashes
+// needs waits in the slot's four padding words (kProbeSlotWords = 20: 16 of block, 4 spare),
+// not in registers.
+__device__ inline void bloom_entry16_park(const Xxh16& x, uint4* slot)
+{
+  slot[4] = uint4{(uint32_t)x.rk1, (uint32_t)(x.rk1 >> 32), (uint32_t)x.k2, (uint32_t)(x.k2 >> 32)};
+}
+
+__device__ inline uint32_t bloom_entry16_test(uint64_t h0, const BloomBits16& bits,
+                                              const BloomEntry16& f, uint4* slot)
+{
+  uint32_t ok = 1;
+  if (f.cls() == kChecked) {
+    const uint4 b0 = f.blk[0], b1 = f.blk[1], b2 = f.blk[2], b3 = f.blk[3];
+    const uint32_t* slot32 = reinterpret_cast<const uint32_t*>(slot);
+    slot[0] = b0;
+    slot[1] = b1;
+    slot[2] = b2;
+    slot[3] = b3;
+    const uint32_t k = f.k();
+    uint32_t bit = (uint32_t)h0 & 511u;
+    // (class < 4 and hash_count < 65536: bit 31 of k_cls is never set)
+    ok = bloom_bits16_and<1>(bits, slot32, k, f.k_cls >> 31, slot32[bit >> 5] >> (bit & 31));
+    if (k > 8) {
+      const uint4 xs = slot[4];
+      Xxh16 x;
+      x.rk1 = (uint64_t)xs.x | ((uint64_t)xs.y << 32);
+      x.k2 = (uint64_t)xs.z | ((uint64_t)xs.w << 32);
+      for (uint32_t j = 8; j < k; ++j) {
+        bit = x.finish_lo9(c_bloom.rhinit16[j]) & 511u;
+        ok &= slot32[bit >> 5] >> (bit & 31);
+      }
+    }
+  }
+  return (ok & 1u) | (f.cls() << 1);
+}
+
+// Keys of other shapes: bloom_probe_item's test with the bit index of hash j supplied by the
+// caller (finished again from the shared lane rounds, or read from the lane's cache).
+template <bool kOpts, typename BitFn>
+__device__ inline uint32_t bloom_entry_test(const uint8_t* __restrict__ filters,
+                                            const tkv_amq_segment* __restrict__ segs, uint32_t n_segs,
+                                            uint32_t leaf, uint64_t h0, const uint64_t* page_ids,
+                                            uint32_t ent, BitFn&& bit_of)
+{
+  const ProbeDesc d = load_probe_desc(segs, leaf, n_segs);
+  if (d.hash_count == 0) return 1u | (kNoFilter << 1);
+  if constexpr (kOpts) {
+    if (!page_id_matches(filters + d.out_offset, 16, page_ids, ent)) return 1u | (kIdMismatch << 1);
+  }
+  const uint64_t* blk = reinterpret_cast<const uint64_t*>(filters + d.out_offset + kBloomHeader +
+                                                          64 * __umul64hi(h0, (uint64_t)d.n_blocks));
+  uint32_t b = (uint32_t)h0 & 511u;
+  uint32_t ok = (uint32_t)(blk[b >> 6] >> (b & 63));
+  for (uint32_t j = 1; j < d.hash_count; ++j) {
+    b = bit_of(j, d.hash_count);
+    ok &= (uint32_t)(blk[b >> 6] >> (b & 63));
+  }
+  return (ok & 1u) | (kChecked << 1);
+}
+
+// Occupancy: the plain 16-byte-key forms ask for 8 waves per SIMD (64 VGPRs), what the pair
+// probes run at.  VQF meets it (57 VGPRs); Bloom stops at 66 VGPRs, 7 waves (the block's 16
+// registers beside the unpacked indices): DESIGN.md section 11.  The forms with options do
+// not ask (held to 64 VGPRs, the VQF one spilled five registers to scratch).  Independent
+// random lines in flight come from the waves, as in the pair probes.
+template <int KIND, int MODE, bool kOpts>
+__global__ __launch_bounds__(256, (MODE == kKey16 && !kOpts ? 8 : 4)) void path_probe_kernel(
+    PathArgs a, tkv_amq_probe_opts opts)
+{
+  // Bloom: the lane's block slot (16-byte keys) or its cache of bit indices (keys of 32 bytes
+  // and more, whose XXH64 has no seed-independent part)
+  __shared__ uint4 s_blk[KIND == TKV_AMQ_BLOOM ? 256 * kProbeSlotWords / 4 : 1];
+  __shared__ uint32_t s_scan[4];
+  const uint32_t tid = threadIdx.x;
+  uint4* slot = s_blk + (KIND == TKV_AMQ_BLOOM ? tid * (kProbeSlotWords / 4) : 0u);
+  ProbeTally t;
+  // without options the grid has one workgroup per 256 queries (no loop: the scan's addresses
+  // would be kept in registers across it); with options it is bounded and strides
+  uint32_t w = blockIdx.x;
+  do {
+    const uint64_t i = (uint64_t)w * 256 + tid;
+    const bool live = i < a.n_queries;
+    uint32_t b = 0, e = 0;
+    if (live) path_range(a, i, b, e);
+    PathWalk wk;
+    if (b < e) {
+      // the next entry's leaf index (Bloom, 16-byte keys: its descriptor too) is read while
+      // this entry is tested
+      uint32_t leaf = a.path_leaf[b];
+      if constexpr (KIND == TKV_AMQ_VQF) {
+        const uint64_t h = vqf_query_hash<MODE>(a.q, a.qoffs, a.stride, i);
+        for (uint32_t ent = b; ent < e; ++ent) {
+          const uint32_t leaf1 = ent + 1 < e ? a.path_leaf[ent + 1] : 0u;
+          const uint32_t r = vqf_probe_one<kOpts>(a.filters, a.segs, a.n_segs, leaf, h,
+                                                  opts.d_query_page_id, ent);
+          wk.record<kOpts>(a, opts, t, r, ent - b, ent);
+          leaf = leaf1;
+        }
+      } else if constexpr (MODE == kKey16) {
+        const uint4 kv = load_nt16(a.q + 16 * i);
+        const Xxh16 x((uint64_t)kv.x | ((uint64_t)kv.y << 32), (uint64_t)kv.z | ((uint64_t)kv.w << 32));
+        const uint64_t h0 = x.finish(c_bloom.rhinit16[0]);
+        const BloomBits16 bits(x);
+        bloom_entry16_park(x, slot);
+        BloomEntry16 cur = bloom_entry16_fetch<kOpts>(a.filters, a.segs, a.n_segs, leaf, h0,
+                                                      opts.d_query_page_id, b);
+        for (uint32_t ent = b; ent < e; ++ent) {
+          BloomEntry16 nxt = cur;
+          if (ent + 1 < e)
+            nxt = bloom_entry16_fetch<kOpts>(a.filters, a.segs, a.n_segs, a.path_leaf[ent + 1], h0,
+                                             opts.d_query_page_id, ent + 1);
+          const uint32_t r = bloom_entry16_test(h0, bits, cur, slot);
+          wk.record<kOpts>(a, opts, t, r, ent - b, ent);
+          cur = nxt;
+        }
+      } else {
+        uint32_t len;
+        const uint8_t* p = key_at<MODE>(a.q, a.qoffs, a.stride, i, len);
+        if (len < 32) {  // seed-independent lane rounds shared by every hash of every filter
+          const XxhShort x(p, len);
+          const uint64_t h0 = x.finish(c_bloom.seed_p5[0]);
+          for (uint32_t ent = b; ent < e; ++ent) {
+            const uint32_t leaf1 = ent + 1 < e ? a.path_leaf[ent + 1] : 0u;
+            const uint32_t r = bloom_entry_test<kOpts>(
+                a.filters, a.segs, a.n_segs, leaf, h0, opts.d_query_page_id, ent,
+                [&](uint32_t j, uint32_t) { return x.finish_lo9(c_bloom.seed_p5[j]) & 511u; });
+            wk.record<kOpts>(a, opts, t, r, ent - b, ent);
+            leaf = leaf1;
+          }
+        } else {
+          // every hash reads the whole key: bit index j is computed when the first filter
+          // with more than j hashes comes by, and kept in the lane's LDS slot
+          uint16_t* cache = reinterpret_cast<uint16_t*>(slot);
+          const uint64_t h0 = xxh64_bytes(p, len, c_bloom.seed[0]);
+          uint32_t have = 1;
+          for (uint32_t ent = b; ent < e; ++ent) {
+            const uint32_t leaf1 = ent + 1 < e ? a.path_leaf[ent + 1] : 0u;
+            const uint32_t r = bloom_entry_test<kOpts>(
+                a.filters, a.segs, a.n_segs, leaf, h0, opts.d_query_page_id, ent,
+                [&](uint32_t j, uint32_t k) {
+                  for (const uint32_t want = min(k, kMaxBloomHashes); have < want; ++have)
+                    cache[have] = (uint16_t)(xxh64_bytes(p, len, c_bloom.seed[have]) & 511u);
+                  return (uint32_t)cache[min(j, kMaxBloomHashes - 1)];
+                });
+            wk.record<kOpts>(a, opts, t, r, ent - b, ent);
+            leaf = leaf1;
+          }
+        }
+      }
+    }
+    if (live) a.mask[i] = wk.mask;
+    uint32_t total;
+    const uint32_t pre = path_block_scan256(wk.cnt, s_scan, &total);
+    if (live) a.cand_begin[i] = pre;
+    if (tid == 0) a.wg_total[w] = total;
+    w += gridDim.x;
+  } while (kOpts && w < a.n_wgs);
+  if constexpr (kOpts) flush_tally(t, opts.d_metrics, opts.d_truth != nullptr);
+}
+
+// One workgroup: wg_total[w] <- sum of wg_total[w'] over w' < w, kPathScanSpan of them per
+// pass with the running base carried over; cand_begin[n_queries] <- the total.  (n_wgs == 0:
+// writes cand_begin[0] = 0, all an empty batch needs.)
+__global__ __launch_bounds__(256) void path_scan_totals(uint32_t* __restrict__ wg_total, uint32_t n_wgs,
+                                                        uint32_t* __restrict__ cand_begin,
+                                                        uint32_t n_queries, uint32_t n_entries)
+{
+  __shared__ uint32_t s[4];
+  const uint32_t tid = threadIdx.x;
+  uint32_t base = 0;
+  for (uint32_t p0 = 0; p0 < n_wgs; p0 += kPathScanSpan) {
+    uint32_t v[kPathScanPerThread];
+    uint32_t sum = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kPathScanPerThread; ++r) {
+      const uint32_t w = p0 + tid * kPathScanPerThread + r;
+      v[r] = w < n_wgs ? wg_total[w] : 0u;
+      sum += v[r];
+    }
+    uint32_t total;
+    uint32_t run = base + path_block_scan256(sum, s, &total);
+#pragma unroll
+    for (uint32_t r = 0; r < kPathScanPerThread; ++r) {
+      const uint32_t w = p0 + tid * kPathScanPerThread + r;
+      if (w < n_wgs) wg_total[w] = run;
+      run += v[r];
+    }
+    base += total;
+  }
+  // (more candidates than entries: only paths that share entries; see path_scatter)
+  if (tid == 0) cand_begin[n_queries] = min(base, n_entries);
+}
+
+// Lane i writes query i's candidates in path order.  Positions at or past n_entries (the
+// capacity) can come up only when paths share entries; those candidates are dropped and the
+// offsets stop at n_entries, so nothing is written out of range.
+__global__ __launch_bounds__(256) void path_scatter(PathArgs a)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_queries) return;
+  uint32_t b, e;
+  path_range(a, i, b, e);
+  uint32_t pos = a.cand_begin[i] + a.wg_total[blockIdx.x];
+  a.cand_begin[i] = min(pos, a.n_entries);
+  uint32_t m = a.mask[i];
+  while (m) {
+    const uint32_t j = (uint32_t)__builtin_ctz(m);
+    m &= m - 1;
+    if (pos < a.n_entries) {
+      a.cand_leaf[pos] = a.path_leaf[b + j];
+      if (a.cand_entry) a.cand_entry[pos] = b + j;
+    }
+    ++pos;
+  }
+  if (e - b > kPathMaskEntries) {
+    for (uint32_t ent = b + kPathMaskEntries; ent < e; ++ent) {
+      if (a.answers[ent] == 0) continue;
+      if (pos < a.n_entries) {
+        a.cand_leaf[pos] = a.path_leaf[ent];
+        if (a.cand_entry) a.cand_entry[pos] = ent;
+      }
+      ++pos;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void gen_keys16_kernel(uint64_t seed, uint64_t first, uint64_t n,
                                                          ulonglong2* __restrict__ out)
 {
@@ -6726,6 +7104,102 @@ int tkv_amq_bloom_probe_hashed_ex(const uint8_t* d_filters, const tkv_amq_segmen
     hipLaunchKernelGGL(bloom_probe_hashed<false>, dim3(probe_grid(n, false)), dim3(256), 0,
                        as_stream(stream), d_filters, d_segs, n_segs, d_query, k_max, d_pair_query, n,
                        d_qseg, d_result, o);
+  return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
+}
+
+// Path probe workspace: a 16-byte header (reserved), the workgroup totals, one answer mask
+// per query, one answer byte per entry (used when the caller passes no d_entry_result).
+struct PathWsLayout {
+  uint64_t n_wgs, totals_off, mask_off, answers_off, bytes;
+};
+
+static PathWsLayout path_ws_layout(uint64_t n_queries, uint64_t n_entries)
+{
+  PathWsLayout l;
+  l.n_wgs = div_up(n_queries, 256);
+  l.totals_off = 16;
+  l.mask_off = l.totals_off + div_up(4 * l.n_wgs, 16) * 16;
+  l.answers_off = l.mask_off + div_up(4 * n_queries, 16) * 16;
+  l.bytes = l.answers_off + div_up(n_entries, 16) * 16;
+  return l;
+}
+
+uint64_t tkv_amq_path_probe_ws_bytes(uint64_t n_queries, uint64_t n_entries)
+{
+  if (n_queries > 0xffffffffull || n_entries > 0xffffffffull) return 0;
+  return path_ws_layout(n_queries, n_entries).bytes;
+}
+
+int tkv_amq_path_probe(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs, uint32_t n_segs,
+                       const uint8_t* q, const uint64_t* qoffs, uint32_t stride, uint64_t n_queries,
+                       const uint32_t* d_path_begin, const uint32_t* d_path_leaf, uint64_t n_entries,
+                       uint8_t* d_entry_result, uint32_t* d_cand_begin, uint32_t* d_cand_leaf,
+                       uint32_t* d_cand_entry, const tkv_amq_probe_opts* opts, void* d_ws,
+                       uint64_t ws_bytes, void* stream)
+{
+  if (tkv_amq_device_count() == 0) return TKV_AMQ_UNAVAILABLE;
+  if (kind != TKV_AMQ_BLOOM && kind != TKV_AMQ_VQF) return TKV_AMQ_INVALID_ARGUMENT;
+  if (n_queries > 0xffffffffull || n_entries > 0xffffffffull) return TKV_AMQ_INVALID_ARGUMENT;
+  const hipStream_t s = as_stream(stream);
+  if (n_queries == 0) {
+    if (d_cand_begin) {
+      hipLaunchKernelGGL(path_scan_totals, dim3(1), dim3(256), 0, s, static_cast<uint32_t*>(nullptr), 0u,
+                         d_cand_begin, 0u, 0u);
+      return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
+    }
+    return TKV_AMQ_OK;
+  }
+  if (!q || !d_path_begin || !d_cand_begin || (!qoffs && !stride)) return TKV_AMQ_INVALID_ARGUMENT;
+  if (n_entries && (!d_filters || !d_segs || n_segs == 0 || !d_path_leaf || !d_cand_leaf))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  const PathWsLayout l = path_ws_layout(n_queries, n_entries);
+  if (!d_ws || ws_bytes < l.bytes || (reinterpret_cast<uintptr_t>(d_ws) & 15))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  const int mode = key_mode(qoffs, stride);
+  if (mode == kKey16 && (reinterpret_cast<uintptr_t>(q) & 15)) return TKV_AMQ_INVALID_ARGUMENT;
+  const tkv_amq_probe_opts o = probe_opts(opts);
+  const bool ex = probe_opts_used(o);
+  uint8_t* ws = static_cast<uint8_t*>(d_ws);
+  PathArgs a;
+  a.filters = d_filters;
+  a.segs = d_segs;
+  a.n_segs = n_segs;
+  a.q = q;
+  a.qoffs = qoffs;
+  a.stride = stride;
+  a.n_queries = (uint32_t)n_queries;
+  a.path_begin = d_path_begin;
+  a.path_leaf = d_path_leaf;
+  a.n_entries = (uint32_t)n_entries;
+  a.every_answer = d_entry_result ? 1u : 0u;
+  a.answers = d_entry_result ? d_entry_result : ws + l.answers_off;
+  a.mask = reinterpret_cast<uint32_t*>(ws + l.mask_off);
+  a.wg_total = reinterpret_cast<uint32_t*>(ws + l.totals_off);
+  a.cand_begin = d_cand_begin;
+  a.cand_leaf = d_cand_leaf;
+  a.cand_entry = d_cand_entry;
+  a.n_wgs = (uint32_t)l.n_wgs;
+  // with options: a bounded grid, so the metrics take one atomic per counter per wave (as
+  // probe_grid does for the pair probes)
+  const dim3 grid(ex && a.n_wgs > 8192u ? 8192u : a.n_wgs), block(256);
+#define TKV_PATH_LAUNCH(KIND, MODE)                                                              \
+  do {                                                                                           \
+    if (ex) hipLaunchKernelGGL((path_probe_kernel<KIND, MODE, true>), grid, block, 0, s, a, o);  \
+    else hipLaunchKernelGGL((path_probe_kernel<KIND, MODE, false>), grid, block, 0, s, a, o);    \
+  } while (0)
+  if (kind == TKV_AMQ_BLOOM) {
+    if (mode == kKey16) TKV_PATH_LAUNCH(TKV_AMQ_BLOOM, kKey16);
+    else if (mode == kKeyFixed) TKV_PATH_LAUNCH(TKV_AMQ_BLOOM, kKeyFixed);
+    else TKV_PATH_LAUNCH(TKV_AMQ_BLOOM, kKeyVar);
+  } else {
+    if (mode == kKey16) TKV_PATH_LAUNCH(TKV_AMQ_VQF, kKey16);
+    else if (mode == kKeyFixed) TKV_PATH_LAUNCH(TKV_AMQ_VQF, kKeyFixed);
+    else TKV_PATH_LAUNCH(TKV_AMQ_VQF, kKeyVar);
+  }
+#undef TKV_PATH_LAUNCH
+  hipLaunchKernelGGL(path_scan_totals, dim3(1), dim3(256), 0, s, a.wg_total, a.n_wgs, d_cand_begin,
+                     a.n_queries, a.n_entries);
+  hipLaunchKernelGGL(path_scatter, dim3(a.n_wgs), block, 0, s, a);
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
 

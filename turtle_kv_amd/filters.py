@@ -697,6 +697,69 @@ def bloom_probe_hashed(plan: FilterPlan, filters, query_hashes, k_max: int, quer
     return out
 
 
+def path_probe_workspace_bytes(n_queries: int, n_entries: int) -> int:
+    """Device workspace tkv_amq_path_probe needs (host only; 0 for counts it refuses)."""
+    return int(abi.lib().tkv_amq_path_probe_ws_bytes(int(n_queries), int(n_entries)))
+
+
+@dataclass
+class PathProbeResult:
+    """What probe_paths leaves on the device: query i's candidates -- the leaves of its path
+    the filters could not reject, in path order -- are cand_leaf[cand_begin[i]:cand_begin[i+1]]
+    (and their entry indices cand_entry[...], if asked for).  Only the first
+    cand_begin[n_queries] elements of cand_leaf / cand_entry are written."""
+    cand_begin: object                   # int32 [n_queries + 1]
+    cand_leaf: object                    # int32 [n_entries] capacity
+    cand_entry: object = None            # int32 [n_entries] capacity, or None
+    entry_result: object = None          # uint8 [n_entries], or None
+    workspace: object = field(default=None, repr=False)
+
+    def total(self) -> int:
+        """Number of candidates (the one call here that synchronises)."""
+        return int(self.cand_begin[-1].item())
+
+
+def probe_paths(plan: FilterPlan, filters, queries: KeyBatch, path_begin, path_leaf, *,
+                entry_result=None, want_entries: bool = False, query_page_ids=None, truth=None,
+                metrics: ProbeMetrics | None = None, workspace=None, stream=None) -> PathProbeResult:
+    """A batched multi-get's filter walk (tkv_amq_path_probe): query i would visit the leaves
+    path_leaf[path_begin[i]:path_begin[i+1]] (segment indices of `plan`, in lookup order); each
+    key is hashed once and every filter on its path is asked reject_page.  Returns the leaves
+    still to search per query, compacted on the device.  entry_result (uint8 [n_entries], or
+    True to allocate it) receives every entry's answer, exactly what the pair probes answer;
+    query_page_ids, truth and metrics are per ENTRY, as they are per pair there.  `workspace`:
+    a caller-owned uint8 tensor of path_probe_workspace_bytes() bytes (e.g. for graph capture)."""
+    torch = _torch()
+    _require_device()
+    dev = filters.device
+    n_entries = int(path_leaf.numel())
+    pb = path_begin.to(dtype=torch.int32).contiguous()
+    pl = path_leaf.to(dtype=torch.int32).contiguous()
+    if pb.numel() != queries.n + 1:
+        raise ValueError("path_begin must have one element per query plus one")
+    if entry_result is True:
+        entry_result = torch.empty(n_entries, dtype=torch.uint8, device=dev)
+    cand_begin = torch.empty(queries.n + 1, dtype=torch.int32, device=dev)
+    cand_leaf = torch.empty(n_entries, dtype=torch.int32, device=dev)
+    cand_entry = torch.empty(n_entries, dtype=torch.int32, device=dev) if want_entries else None
+    need = path_probe_workspace_bytes(queries.n, n_entries)
+    if need == 0:
+        raise TkvAmqError(abi.INVALID_ARGUMENT, "tkv_amq_path_probe: too many queries or entries")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    o, _keep = _probe_opts(query_page_ids, truth, metrics)
+    used = query_page_ids is not None or truth is not None or metrics is not None
+    st = abi.lib().tkv_amq_path_probe(plan.kind, _ptr(filters), _ptr(plan.device_segs(dev)),
+                                      plan.n_segs, _ptr(queries.data), _ptr(queries.offsets),
+                                      queries.stride, queries.n, _ptr(pb), _ptr(pl), n_entries,
+                                      _ptr(entry_result), _ptr(cand_begin), _ptr(cand_leaf),
+                                      _ptr(cand_entry), ctypes.byref(o) if used else None,
+                                      _ptr(workspace), int(workspace.numel()), _stream_handle(stream))
+    _hold(stream, pb, pl, workspace, *_keep)
+    abi.check(st, "tkv_amq_path_probe")
+    return PathProbeResult(cand_begin, cand_leaf, cand_entry, entry_result, workspace)
+
+
 # ---------------------------------------------------------------------------------------
 # single-leaf API (the reference's per-leaf entry points)
 # ---------------------------------------------------------------------------------------
