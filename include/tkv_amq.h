@@ -44,6 +44,14 @@
  *                           nodes.hpp:158-187, segmented_levels.hpp:358-369): each key hashed
  *                           once, reject_page asked of every filter on its path, the leaves
  *                           still to search returned per query, in order
+ *   tkv_amq_open_filters    what KeyQuery::reject_page reads from a loaded filter page instead
+ *                           of a plan (tree/key_query.hpp:149-247): check_magic()
+ *                           (vqf_filter_page_view.hpp:96-100), src_page_id, block_count,
+ *                           hash_count, the VQF hash_mask and vqf_metadata -- for a batch of
+ *                           stored payloads or page images, validated, as probe segments
+ *   tkv_amq_scan_filters    no reference counterpart: a read-only scrub of the filter bytes
+ *                           (set bits per Bloom filter, occupied slots and the block invariants
+ *                           of vqf_init_in_place / vqf_insert per VQF)
  *   tkv_amq_stage_keys      the EditView key range build_filter_for_leaf_in_job iterates
  *                           (core/merge_compactor.hpp:107-139) gathered into one contiguous
  *                           host key buffer for the H2D copy (host only)
@@ -475,6 +483,93 @@ int tkv_amq_path_probe(int kind, const uint8_t* d_filters, const tkv_amq_segment
                        uint64_t n_entries, uint8_t* d_entry_result, uint32_t* d_cand_begin,
                        uint32_t* d_cand_leaf, uint32_t* d_cand_entry, const tkv_amq_probe_opts* opts,
                        void* d_workspace, uint64_t workspace_bytes, void* stream);
+
+/* Open built filters without a plan (a store restarting on a checkpoint, filter pages received
+ * from elsewhere): reconstructs and validates one segment per filter from the filter bytes on
+ * the device -- what KeyQuery::reject_page reads from the page itself (tree/key_query.hpp:
+ * 149-247; check_magic, vqf_filter_page_view.hpp:96-100).  Where filter s lives:
+ *  d_offsets != NULL    (device, n_filters entries) its payload starts at d_offsets[s] and may
+ *                       extend to total_bytes
+ *  stride != 0          it starts at s * stride and may extend to min((s+1) * stride, total_bytes)
+ *  page_size_log2 != 0  (7..31) slot s is a whole page at s << page_size_log2, the payload 64
+ *                       bytes in (tkv_amq_plan_pages' layout), bounded by the page and the
+ *                       buffer; the PackedPageHeader fields the builders set (layout_id,
+ *                       unused_begin, unused_end, size) must agree with the kind, the payload
+ *                       size and the page size, and the segment gets the plan's page_flags
+ * Exactly one of the three forms.  d_filters must be 16-byte aligned.  Per filter, in this order
+ * (every read is preceded by the check that it lies inside the bound):
+ *  1. the start lies inside the buffer (OUT_OF_BOUNDS), is 16-byte aligned (MISALIGNED), and the
+ *     header -- 64 bytes Bloom, 80 VQF -- fits the bound (OUT_OF_BOUNDS)
+ *  2. the magic: the other kind's is WRONG_KIND, anything else but this kind's BAD_MAGIC
+ *  3. the fields that stand alone (BAD_GEOMETRY).  Bloom: layout == 2, 1 <= hash_count <= 32,
+ *     block_count >= 1.  VQF: hash_seed is the VQF seed, hash_mask == ~0 << shift for a shift in
+ *     0..63, key_remainder_bits 8 or 16, 1 <= nblocks <= 2^24
+ *  4. the payload the block count names -- 64 + 64 * block_count, 32 + 48 + 64 * nblocks -- fits
+ *     the bound and a uint32_t (OUT_OF_BOUNDS)
+ *  5. the fields derived from the block count (BAD_GEOMETRY).  Bloom: bit_count == 512 *
+ *     block_count, word_count == 8 * block_count (xxh3_checksum is not interpreted: the builders
+ *     write 0).  VQF: total_size_in_bytes == 64 * nblocks, range == nblocks * buckets << tag
+ *     bits, nslots == nblocks * slots, nelts <= nslots
+ *  6. a page image's header fields (BAD_PAGE)
+ * So a block count that points past its slot is OUT_OF_BOUNDS, and one that fits but disagrees
+ * with the other fields BAD_GEOMETRY.
+ * A filter that passes gets the segment the plan would have produced in out_offset, n_blocks,
+ * hash_count, tag_bits, hash_val_shift, mod_magic, src_page_id, payload_bytes and page_flags;
+ * n_keys is the header's item_count (Bloom) or nelts (VQF: the keys hash_val_shift did not
+ * drop), saturated to 32 bits; bits_per_key, key_begin and block_base, which the page does not
+ * record, are 0.  Opened segments serve the probes and tkv_amq_scan_filters; BUILDING INTO THEM
+ * IS NOT SUPPORTED.  A filter that fails gets its out_offset and otherwise the all-zero "no
+ * filter" segment, so every probe answers 1 (kUnknown) for it and reads none of its bytes.
+ *  d_status[n_filters]  (device) the code of every filter
+ *  d_summary[7]         (device, or NULL) the count of each code; zeroed by the call
+ * Asynchronous on `stream`, capturable: one kernel launch (after a 28-byte memset node for
+ * d_summary, if given); no allocation, no synchronisation.  n_filters == 0 is OK.
+ * InvalidArgument: unknown kind, not exactly one location form (with n_filters > 0; more than
+ * one always), page_size_log2 outside 7..31, a misaligned d_filters, a null required buffer.
+ * Both entry points judge their arguments before they look for a device, so a bad call is
+ * InvalidArgument everywhere and a good one is Unavailable where no device is visible. */
+#define TKV_AMQ_OPEN_OK 0u
+#define TKV_AMQ_OPEN_BAD_MAGIC 1u     /* neither kind's magic (all-zero included) */
+#define TKV_AMQ_OPEN_WRONG_KIND 2u    /* the other kind's magic */
+#define TKV_AMQ_OPEN_BAD_GEOMETRY 3u  /* header fields disagree with each other or the spec */
+#define TKV_AMQ_OPEN_OUT_OF_BOUNDS 4u /* header or payload does not fit its slot / the buffer */
+#define TKV_AMQ_OPEN_MISALIGNED 5u    /* payload offset not 16-byte aligned */
+#define TKV_AMQ_OPEN_BAD_PAGE 6u      /* page-image form: PackedPageHeader fields disagree */
+int tkv_amq_open_filters(int kind, const uint8_t* d_filters, uint64_t total_bytes,
+                         const uint64_t* d_offsets, uint64_t stride, uint32_t page_size_log2,
+                         uint32_t n_filters, tkv_amq_segment* d_segs, uint32_t* d_status,
+                         uint32_t* d_summary, void* stream);
+
+/* One read-only pass over the blocks of every filter (plan segments or opened ones; a "no
+ * filter" segment gives all-zero stats): what is in the filter bytes.
+ * VQF block rules (what vqf_init_in_place and vqf_insert leave behind).  With
+ * W = 128 metadata bits, B = 80 buckets, S = 48 slots for 8-bit tags and W = 64, B = 36, S = 28
+ * for 16-bit tags: occ = select(md, B-1) - (B-1), the zeros below the B-th set bit.  A block is
+ * bad if md has fewer than B set bits or occ > S (it then counts as bad only: it adds nothing to
+ * occupied, full_blocks, empty_blocks or max_block), if popcount(md) is not W-1 (occ == 0) or
+ * W-occ (otherwise), or if one of the tag slots occ .. S-1 is not zero.
+ * The work is split by bytes, not by segment: chunks of 256 blocks (16 KiB), located through a
+ * device-side prefix over the segments' chunk counts in the workspace, so 6,104 leaves of 20 KB
+ * and one filter of 1.5 GB take the same path.  Integer atomics only: the output is a function
+ * of the input.  The call zeroes d_stats itself.
+ *  d_stats[n_segs]  (device, 16-byte aligned)
+ *  d_workspace      tkv_amq_scan_filters_ws_bytes(n_segs) bytes (host function: >= 16,
+ *                   monotone), 16-byte aligned
+ * Asynchronous on `stream`, capturable (four kernel launches); no allocation, no
+ * synchronisation.  n_segs == 0 is OK.  InvalidArgument: unknown kind, a null buffer with
+ * n_segs > 0, a short or misaligned workspace, misaligned d_filters or d_stats. */
+typedef struct tkv_amq_filter_stats { /* 32 bytes */
+  uint64_t occupied;     /* Bloom: set bits; VQF: occupied tag slots, summed over blocks */
+  uint64_t header_items; /* Bloom item_count / VQF nelts as stored in the payload */
+  uint32_t full_blocks;  /* Bloom: all 512 bits set; VQF: no free slot */
+  uint32_t empty_blocks; /* nothing set / no tag */
+  uint32_t max_block;    /* largest per-block count (bits or slots) */
+  uint32_t bad_blocks;   /* VQF: blocks that break a rule above; Bloom: 0 */
+} tkv_amq_filter_stats;
+uint64_t tkv_amq_scan_filters_ws_bytes(uint32_t n_segs);
+int tkv_amq_scan_filters(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs,
+                         uint32_t n_segs, tkv_amq_filter_stats* d_stats, void* d_workspace,
+                         uint64_t workspace_bytes, void* stream);
 
 /* Key staging, host only (no device needed): the H2D front end.  The reference passes the
  * build a flattened range of EditView whose keys are KeyView = std::string_view into leaf /

@@ -16,6 +16,8 @@
 //   TreeOptions (filter sizing)           tree/tree_options.hpp:149-258    TreeOptions
 //   FilterPageAlloc page image            tree/filter_builder.hpp:58-105,231-237,293-296
 //                                                                          FilterBatchBuilder::plan_pages
+//   reject_page's read of a loaded page   tree/key_query.hpp:149-247, vqf_filter_page_view.hpp:96-100
+//                                                                          open_filter_pages, scan_filters
 //
 // The single-leaf functions take the leaf's keys as host string views (the reference's
 // `items` range of EditView keys, tombstones included) and fill a host page payload
@@ -317,6 +319,100 @@ class FilterBatchBuilder
   bool planned_ = false;
   DeviceBuffer d_segs_, d_ws_;
 };
+
+// ---------------------------------------------------------------------------------------
+// open built filter pages without a plan, and scan their fill (tkv_amq_open_filters,
+// tkv_amq_scan_filters): a store restarting on a checkpoint has filter bytes and no plan
+// ---------------------------------------------------------------------------------------
+// Where filter s lives in the device buffer -- exactly one of: d_offsets[s] (device array),
+// s * stride, or the page s << page_size_log2 (FilterBatchBuilder::pages' layout).
+struct FilterLocation {
+  const u64* d_offsets = nullptr;
+  u64 stride = 0;
+  u32 page_size_log2 = 0;
+};
+
+// The segments the device reconstructed from the filter bytes (host copy and the device copy
+// the probes take), each filter's TKV_AMQ_OPEN_* code and the count of each code.  A filter
+// that failed is a "no filter" segment: every probe answers 1 (kUnknown) for it.  The segments
+// serve the probes and scan_filters; building into them is not supported.
+struct OpenedFilterPages {
+  std::vector<tkv_amq_segment> segments;
+  std::vector<u32> status;
+  u32 summary[7] = {0, 0, 0, 0, 0, 0, 0};
+  DeviceBuffer d_segments;
+
+  bool all_ok() const { return summary[TKV_AMQ_OPEN_OK] == status.size(); }
+  const tkv_amq_segment* device_segments() const { return d_segments.get<tkv_amq_segment>(); }
+};
+
+// Synchronises `stream` (the segments and codes are copied back).
+inline Status open_filter_pages(FilterKind kind, const u8* d_filters, u64 total_bytes,
+                                const FilterLocation& where, u32 n_filters, OpenedFilterPages& out,
+                                hipStream_t stream = nullptr)
+{
+  out.segments.assign(n_filters, tkv_amq_segment{});
+  out.status.assign(n_filters, 0);
+  if (tkv_amq_device_count() == 0) {
+    // nothing can be allocated: the entry point's own answer (InvalidArgument for a bad call,
+    // else Unavailable); it launches nothing, so host stand-ins serve as its output buffers
+    tkv_amq_segment g{};
+    u32 w[7];
+    return Status::from(tkv_amq_open_filters((int)kind, d_filters, total_bytes, where.d_offsets, where.stride,
+                                             where.page_size_log2, n_filters, &g, w, w, stream),
+                        "tkv_amq_open_filters");
+  }
+  DeviceBuffer d_status, d_summary;
+  if (!out.d_segments.resize(sizeof(tkv_amq_segment) * n_filters) || !d_status.resize(4 * usize{n_filters}) ||
+      !d_summary.resize(sizeof(out.summary)))
+    return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+  const int st = tkv_amq_open_filters((int)kind, d_filters, total_bytes, where.d_offsets, where.stride,
+                                      where.page_size_log2, n_filters, out.d_segments.get<tkv_amq_segment>(),
+                                      d_status.get<u32>(), d_summary.get<u32>(), stream);
+  if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_open_filters");
+  if (hipMemcpyAsync(out.segments.data(), out.d_segments.get(), sizeof(tkv_amq_segment) * n_filters,
+                     hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipMemcpyAsync(out.status.data(), d_status.get(), 4 * usize{n_filters}, hipMemcpyDeviceToHost, stream) !=
+          hipSuccess ||
+      hipMemcpyAsync(out.summary, d_summary.get(), sizeof(out.summary), hipMemcpyDeviceToHost, stream) !=
+          hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy opened segments");
+  return OkStatus();
+}
+
+// One read-only pass over every filter's blocks (plan segments or opened ones): set bits /
+// occupied slots, the header's item count, full / empty blocks, the fullest block, and the VQF
+// blocks that break a block invariant.  Synchronises `stream`.
+inline Status scan_filters(FilterKind kind, const u8* d_filters, const tkv_amq_segment* d_segs, u32 n_segs,
+                           std::vector<tkv_amq_filter_stats>& out, hipStream_t stream = nullptr)
+{
+  out.assign(n_segs, tkv_amq_filter_stats{});
+  const u64 ws_bytes = tkv_amq_scan_filters_ws_bytes(n_segs);
+  if (tkv_amq_device_count() == 0)
+    return Status::from(n_segs && (!d_filters || !d_segs) ? TKV_AMQ_INVALID_ARGUMENT : TKV_AMQ_UNAVAILABLE,
+                        "tkv_amq_scan_filters");
+  DeviceBuffer d_stats, d_ws;
+  if (!d_stats.resize(sizeof(tkv_amq_filter_stats) * usize{n_segs}) || !d_ws.resize(ws_bytes))
+    return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+  const int st = tkv_amq_scan_filters((int)kind, d_filters, d_segs, n_segs, d_stats.get<tkv_amq_filter_stats>(),
+                                      d_ws.get(), ws_bytes, stream);
+  if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_scan_filters");
+  if (hipMemcpyAsync(out.data(), d_stats.get(), sizeof(tkv_amq_filter_stats) * usize{n_segs},
+                     hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy stats");
+  return OkStatus();
+}
+
+// occupied / capacity of one scanned filter: set bits over 512 * n_blocks (Bloom), occupied tag
+// slots over n_blocks * slots (VQF); 0 without a filter
+inline double filter_fill(const tkv_amq_segment& seg, const tkv_amq_filter_stats& st)
+{
+  const double per = seg.hash_count ? 512.0 : seg.tag_bits == 8 ? 48.0 : seg.tag_bits == 16 ? 28.0 : 0.0;
+  const double cap = per * (double)seg.n_blocks;
+  return cap > 0 ? (double)st.occupied / cap : 0.0;
+}
 
 // ---------------------------------------------------------------------------------------
 // single-leaf entry points (host keys -> host page payload)

@@ -12,7 +12,9 @@ from .filters import (BoolStatus, FilterPage, FilterPlan, KeyBatch, KeyQuery, Pa
                       stage_keys, BloomFilterMetrics, QuotientFilterMetrics,
                       plan_filter_stats, record_filter_metrics, TreeOptions, plan_filter_pages,
                       page_header_fields, ProbeMetrics, KeyQueryMetrics, probe_paths,
-                      PathProbeResult, path_probe_workspace_bytes)
+                      PathProbeResult, path_probe_workspace_bytes, OpenedFilters, open_filters,
+                      open_filters_device, scan_filters, scan_filters_device,
+                      scan_filters_workspace_bytes, filter_fill)
 
 __all__ = [
     "abi", "BLOOM", "VQF", "TkvAmqError", "BoolStatus", "FilterPage", "FilterPlan", "KeyBatch",
@@ -23,5 +25,7 @@ __all__ = [
     "bloom_probe_hashed", "HostFilterPipeline", "key_views", "stage_keys",
     "BloomFilterMetrics", "QuotientFilterMetrics", "plan_filter_stats", "record_filter_metrics",
     "TreeOptions", "plan_filter_pages", "page_header_fields", "ProbeMetrics", "KeyQueryMetrics",
-    "probe_paths", "PathProbeResult", "path_probe_workspace_bytes",
+    "probe_paths", "PathProbeResult", "path_probe_workspace_bytes", "OpenedFilters",
+    "open_filters", "open_filters_device", "scan_filters", "scan_filters_device",
+    "scan_filters_workspace_bytes", "filter_fill",
 ]

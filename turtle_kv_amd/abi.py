@@ -94,7 +94,20 @@ EXPORTS = [
     "tkv_amq_bloom_records_per_key", "tkv_amq_bloom_route_records_any_ws_bytes",
     "tkv_amq_bloom_route_records_any",
     "tkv_amq_path_probe_ws_bytes", "tkv_amq_path_probe",
+    "tkv_amq_open_filters", "tkv_amq_scan_filters_ws_bytes", "tkv_amq_scan_filters",
 ]
+
+# tkv_amq_open_filters' per-filter codes (TKV_AMQ_OPEN_*)
+OPEN_OK, OPEN_BAD_MAGIC, OPEN_WRONG_KIND, OPEN_BAD_GEOMETRY, OPEN_OUT_OF_BOUNDS, OPEN_MISALIGNED, \
+    OPEN_BAD_PAGE = range(7)
+OPEN_STATUS_NAMES = ("OK", "BadMagic", "WrongKind", "BadGeometry", "OutOfBounds", "Misaligned",
+                     "BadPage")
+
+# tkv_amq_filter_stats (32 bytes)
+FILTER_STATS_DTYPE = np.dtype([
+    ("occupied", "<u8"), ("header_items", "<u8"), ("full_blocks", "<u4"), ("empty_blocks", "<u4"),
+    ("max_block", "<u4"), ("bad_blocks", "<u4")])
+assert FILTER_STATS_DTYPE.itemsize == 32
 
 
 class RoutePlan(ctypes.Structure):
@@ -206,6 +219,13 @@ def lib(build_if_missing: bool = True):
         L.tkv_amq_path_probe.restype = i32
         L.tkv_amq_path_probe.argtypes = [i32, vp, vp, u32, vp, vp, u32, u64, vp, vp, u64, vp, vp, vp,
                                          vp, popts, vp, u64, vp]
+    if hasattr(L, "tkv_amq_open_filters"):
+        L.tkv_amq_open_filters.restype = i32
+        L.tkv_amq_open_filters.argtypes = [i32, vp, u64, vp, u64, u32, u32, vp, vp, vp, vp]
+        L.tkv_amq_scan_filters_ws_bytes.restype = u64
+        L.tkv_amq_scan_filters_ws_bytes.argtypes = [u32]
+        L.tkv_amq_scan_filters.restype = i32
+        L.tkv_amq_scan_filters.argtypes = [i32, vp, vp, u32, vp, vp, u64, vp]
     if hasattr(L, "tkv_amq_bloom_route"):
         L.tkv_amq_bloom_route_ws_bytes.restype = u64
         L.tkv_amq_bloom_route_ws_bytes.argtypes = [u64, u32]

@@ -17,6 +17,9 @@ replaces it:
   KeyQuery::Metrics                       tree/key_query.hpp:36-60        -> KeyQueryMetrics
   FilterPageAlloc page + header fields    tree/filter_builder.hpp:58-105,231-237,293-296
                                                                           -> plan_filter_pages
+  reject_page's read of a loaded page     tree/key_query.hpp:149-247, vqf_filter_page_view.hpp:96-100
+                                                                          -> open_filters,
+                                                                             FilterPage.from_payload
 
 Device memory, streams and multi-GPU plumbing come from PyTorch-ROCm; every filter
 computation runs in the HIP kernels of libtkv_amq.so.  There is no CPU fallback: with no
@@ -761,6 +764,123 @@ def probe_paths(plan: FilterPlan, filters, queries: KeyBatch, path_begin, path_l
 
 
 # ---------------------------------------------------------------------------------------
+# open built filters without a plan / scan their fill
+# ---------------------------------------------------------------------------------------
+@dataclass
+class OpenedFilters:
+    """What open_filters read from a buffer of built filters: a FilterPlan made of the segments
+    the device reconstructed (it serves probe_filters, the hashed probes, probe_paths and
+    scan_filters; building into it is not supported), the per-filter abi.OPEN_* code and the
+    count of each code.  A filter that failed is a "no filter" segment of the plan: every probe
+    answers 1 (kUnknown) for it."""
+    plan: FilterPlan
+    status: np.ndarray                   # uint32 [n_filters]
+    summary: np.ndarray                  # uint32 [7]
+
+    @property
+    def all_ok(self) -> bool:
+        return int(self.summary[abi.OPEN_OK]) == len(self.status)
+
+
+def open_filters_device(kind: int, filters, n_filters: int, d_segs, d_status, d_summary=None,
+                        offsets=None, stride: int = 0, page_size_log2: int = 0, stream=None) -> None:
+    """The launch alone (tkv_amq_open_filters): device buffers in, nothing copied back, so it can
+    be captured.  d_segs: uint8 [64 * n_filters]; d_status: int32 [n_filters]; d_summary: int32
+    [7] or None; offsets: int64 [n_filters] on the device, or None."""
+    _require_device()
+    total = int(filters.numel()) if filters is not None else 0
+    st = abi.lib().tkv_amq_open_filters(kind, _ptr(filters), total, _ptr(offsets), int(stride),
+                                        int(page_size_log2), int(n_filters), _ptr(d_segs),
+                                        _ptr(d_status), _ptr(d_summary), _stream_handle(stream))
+    abi.check(st, "tkv_amq_open_filters")
+
+
+def open_filters(kind: int, filters, offsets=None, stride: int = 0, page_size_log2: int = 0,
+                 n_filters: int | None = None, stream=None) -> OpenedFilters:
+    """Reconstruct and validate the segments of built filters from their bytes (a store
+    restarting on a checkpoint, filter pages received from elsewhere).  `filters`: device uint8
+    tensor.  Filter s lives at offsets[s] (payloads), at s * stride (payload slots) or in the
+    page s << page_size_log2 (page images, as plan_filter_pages lays them out); n_filters
+    defaults to len(offsets) or the number of whole slots in the buffer."""
+    torch = _torch()
+    _require_device()
+    dev = filters.device
+    d_off = None
+    if offsets is not None:
+        d_off = (offsets if hasattr(offsets, "data_ptr") else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64)).view(np.int64))).to(
+                device=dev, dtype=torch.int64).contiguous()
+        n = int(d_off.numel()) if n_filters is None else int(n_filters)
+    elif n_filters is not None:
+        n = int(n_filters)
+    elif stride:
+        n = -(-int(filters.numel()) // int(stride))
+    elif page_size_log2:
+        n = -(-int(filters.numel()) >> int(page_size_log2))
+    else:
+        raise TkvAmqError(abi.INVALID_ARGUMENT, "open_filters: offsets, stride or page_size_log2")
+    d_segs = torch.empty(max(n, 1) * 64, dtype=torch.uint8, device=dev)
+    d_status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    d_summary = torch.empty(7, dtype=torch.int32, device=dev)
+    open_filters_device(kind, filters, n, d_segs, d_status, d_summary, d_off, stride,
+                        page_size_log2, stream)
+    _hold(stream, d_off, d_segs, d_status, d_summary)
+    if stream is not None:
+        stream.synchronize()
+    segs = d_segs[:64 * n].cpu().numpy().view(abi.SEGMENT_DTYPE).copy()
+    status = d_status[:n].cpu().numpy().view(np.uint32).copy()
+    summary = d_summary.cpu().numpy().view(np.uint32).copy()
+    plan = FilterPlan(kind, 0, segs, int(filters.numel()), 0,
+                      int(segs["n_blocks"].max()) if n else 0, int(segs["n_keys"].sum()) if n else 0)
+    plan._device[str(d_segs.device)] = d_segs[:64 * n] if n else d_segs[:0]
+    return OpenedFilters(plan, status, summary)
+
+
+def scan_filters_workspace_bytes(n_segs: int) -> int:
+    """Device workspace tkv_amq_scan_filters needs (host only)."""
+    return int(abi.lib().tkv_amq_scan_filters_ws_bytes(int(n_segs)))
+
+
+def scan_filters_device(kind: int, filters, d_segs, n_segs: int, d_stats, workspace, stream=None) -> None:
+    """The launches alone (tkv_amq_scan_filters), capturable.  d_stats: uint8 [32 * n_segs]."""
+    _require_device()
+    st = abi.lib().tkv_amq_scan_filters(kind, _ptr(filters), _ptr(d_segs), int(n_segs), _ptr(d_stats),
+                                        _ptr(workspace), int(workspace.numel()) if workspace is not None else 0,
+                                        _stream_handle(stream))
+    abi.check(st, "tkv_amq_scan_filters")
+
+
+def scan_filters(plan: FilterPlan, filters, stream=None) -> np.ndarray:
+    """One read-only pass over the blocks of every filter of `plan` (built or opened): a
+    FILTER_STATS_DTYPE record per filter -- set bits (Bloom) or occupied tag slots (VQF), the
+    item count the payload header stores, full / empty blocks, the fullest block, and the VQF
+    blocks that break a block invariant."""
+    torch = _torch()
+    _require_device()
+    dev = filters.device
+    n = plan.n_segs
+    d_stats = torch.empty(max(n, 1) * 32, dtype=torch.uint8, device=dev)
+    ws = torch.empty(scan_filters_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    scan_filters_device(plan.kind, filters, plan.device_segs(dev), n, d_stats, ws, stream)
+    _hold(stream, d_stats, ws)
+    if stream is not None:
+        stream.synchronize()
+    return d_stats[:32 * n].cpu().numpy().view(abi.FILTER_STATS_DTYPE).copy()
+
+
+def filter_fill(plan: FilterPlan, stats: np.ndarray) -> np.ndarray:
+    """Per filter: the fraction of its bits that are set (Bloom: occupied / (512 * n_blocks)) or
+    of its tag slots that are taken (VQF: occupied / (n_blocks * slots)); 0 without a filter."""
+    nb = plan.segs["n_blocks"].astype(np.float64)
+    if plan.kind == BLOOM:
+        cap = 512.0 * nb * (plan.segs["hash_count"] != 0)
+    else:
+        t = plan.segs["tag_bits"]
+        cap = nb * np.where(t == 8, 48.0, np.where(t == 16, 28.0, 0.0))
+    occ = stats["occupied"].astype(np.float64)
+    return np.divide(occ, cap, out=np.zeros_like(occ), where=cap > 0)
+
+# ---------------------------------------------------------------------------------------
 # single-leaf API (the reference's per-leaf entry points)
 # ---------------------------------------------------------------------------------------
 @dataclass
@@ -770,6 +890,25 @@ class FilterPage:
     payload: object          # device uint8 tensor (page payload bytes)
     plan: FilterPlan
     leaf_page_id: int
+    load_status: int = 0     # abi.OPEN_* of from_payload (0: a planned page, or opened fine)
+
+    @classmethod
+    def from_payload(cls, kind: int, payload) -> "FilterPage":
+        """A filter page from its bare payload bytes (device uint8 tensor, or host bytes that are
+        uploaded), with no plan: the one-segment plan comes from the payload itself
+        (open_filters), as reject_page reads a loaded page (tree/key_query.hpp:149-247).  A
+        payload that does not open keeps its code in load_status: reject_page then answers
+        kUnknown for every key and counts filter_page_load_failed_count."""
+        torch = _torch()
+        if not hasattr(payload, "data_ptr"):
+            host = np.frombuffer(bytes(payload), dtype=np.uint8) if not isinstance(payload, np.ndarray) \
+                else np.ascontiguousarray(payload, dtype=np.uint8)
+            payload = torch.from_numpy(host.copy() if len(host) else np.zeros(1, np.uint8)).cuda()[:len(host)]
+        if not payload.is_contiguous() or payload.data_ptr() % 16:
+            payload = payload.clone()
+        opened = open_filters(kind, payload, offsets=[0])
+        return cls(kind, payload, opened.plan, int(opened.plan.segs[0]["src_page_id"]),
+                   int(opened.status[0]))
 
     @property
     def filter_size(self) -> int:
@@ -919,6 +1058,9 @@ class KeyQuery:
         m.total_filter_query_count.add(n)
         if filter_page is None:
             m.no_filter_page_count.add(n)
+            return [BoolStatus.kUnknown] * n
+        if filter_page.load_status != abi.OPEN_OK:  # the page could not be loaded (:183)
+            m.filter_page_load_failed_count.add(n)
             return [BoolStatus.kUnknown] * n
         hdr = filter_page.payload[:32].cpu().numpy().view("<u8")
         magic = int(hdr[0])
