@@ -207,6 +207,56 @@ int tkv_amq_build_ex(int kind, const uint8_t* keys, const uint64_t* key_offsets,
                      uint32_t n_segs, uint32_t max_blocks, uint8_t* d_out, void* d_workspace,
                      uint64_t workspace_bytes, void* stream);
 
+/* The route a build takes ("Build routes").  Bloom: `route` is the batch's route.
+ * VQF: `route` is the decide stage and `place` the place stage. */
+#define TKV_AMQ_ROUTE_SPLIT 0u         /* Bloom: each leaf's keys over `parts` workgroups, merged */
+#define TKV_AMQ_ROUTE_WINDOW 1u        /* Bloom: `windows` LDS windows per leaf, `parts` per window */
+#define TKV_AMQ_ROUTE_LDS 2u           /* Bloom: one workgroup of `threads` per leaf */
+#define TKV_AMQ_ROUTE_TILED_KEYS 3u    /* Bloom: one filter, tiled, from its 16- or 24-byte keys */
+#define TKV_AMQ_ROUTE_TILED_RECORDS 4u /* Bloom: one filter, tiled, from hashed bit records */
+#define TKV_AMQ_ROUTE_ATOMICS 5u       /* Bloom: device atomics */
+#define TKV_AMQ_ROUTE_VQF_BIG_U8 16u      /* vqf_decide_big, u8 counts in LDS */
+#define TKV_AMQ_ROUTE_VQF_BIG_GLOBAL 17u  /* vqf_decide_big, counts in the workspace */
+#define TKV_AMQ_ROUTE_VQF_RING_PLACE 18u  /* vqf_ring_place, one workgroup per CU */
+#define TKV_AMQ_ROUTE_VQF_RING_PLACE2 19u /* vqf_ring_place, two workgroups per CU */
+#define TKV_AMQ_ROUTE_VQF_RING 20u        /* vqf_decide_ring */
+#define TKV_AMQ_ROUTE_VQF_DECIDE 21u      /* vqf_decide */
+#define TKV_AMQ_PLACE_NONE 0u      /* Bloom, or placed by the decide stage (vqf_ring_place) */
+#define TKV_AMQ_PLACE_FUSED512 1u  /* vqf_place_fused, 512 threads */
+#define TKV_AMQ_PLACE_FUSED256 2u  /* vqf_place_fused, 256 threads */
+#define TKV_AMQ_PLACE_SCATTER 3u   /* vqf_scatter, then vqf_place */
+/* tkv_amq_build_ex's leaves (leaf_route) */
+#define TKV_AMQ_LEAF_BATCH 0u         /* in the compacted batch `out` describes */
+#define TKV_AMQ_LEAF_MULTI 1u         /* tiled, in a multi-leaf launch */
+#define TKV_AMQ_LEAF_TILED_KEYS 2u    /* tiled alone, from its keys */
+#define TKV_AMQ_LEAF_TILED_RECORDS 3u /* tiled alone, from bit records */
+#define TKV_AMQ_LEAF_ATOMICS 4u       /* device atomics */
+#define TKV_AMQ_LEAF_NONE 5u          /* no filter (bits_per_key 0) */
+
+struct tkv_amq_build_route { /* 40 bytes */
+  uint32_t route;         /* TKV_AMQ_ROUTE_* */
+  uint32_t place;         /* TKV_AMQ_PLACE_* */
+  uint32_t parts;         /* workgroups per leaf (split), per window (window) or per leaf (place) */
+  uint32_t windows;       /* LDS windows per leaf (window route), else 0 */
+  uint32_t threads;       /* the build kernel's workgroup size (VQF: the decide stage's) */
+  uint32_t located;       /* VQF: vqf_locate_keys runs ahead of vqf_ring_place */
+  uint64_t ws_bytes;      /* the workspace the route needs */
+  uint32_t lds_bytes;     /* Bloom: a workgroup's LDS image (0: tiled, atomics); VQF: the decide
+                             stage's dynamic LDS */
+  uint32_t reserved;
+};
+
+/* The route tkv_amq_build / tkv_amq_build_ex would take.  Pure host: no device needed.
+ * keys_aligned8: the key pointer is 8-byte aligned (24-byte keys then load as three u64).
+ * h_segs == NULL: tkv_amq_build of n_segs leaves holding n_keys keys.  With h_segs (the plan's
+ * segments): tkv_amq_build_ex; leaf_route[i] (may be NULL) is leaf i's TKV_AMQ_LEAF_*, `out`
+ * describes the compacted batch of the TKV_AMQ_LEAF_BATCH leaves (ws_bytes: after the leaf
+ * list), and is zeroed when there is none.  have_workspace 0: no workspace pointer. */
+int tkv_amq_build_route(int kind, uint32_t key_stride, int has_offsets, int keys_aligned8,
+                        uint32_t n_segs, uint64_t n_keys, uint32_t max_blocks,
+                        const tkv_amq_segment* h_segs, int have_workspace, uint64_t workspace_bytes,
+                        struct tkv_amq_build_route* out, uint8_t* leaf_route);
+
 /* Synchronises `stream`; returns TKV_AMQ_OK, TKV_AMQ_INTERNAL (a VQF block overflowed) or
  * TKV_AMQ_INVALID_ARGUMENT (the workspace was smaller than the plan).  Bloom builds cannot
  * fail on the device. */

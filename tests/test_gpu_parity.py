@@ -692,10 +692,11 @@ def test_bloom_monolithic_large_sampled_oracle(oracle, amq, torch, n, bpk, parts
 
 @pytest.mark.parametrize("shape", ["k16", "k24", "var"])
 def test_bloom_big_leaves_in_lds(oracle, amq, torch, shape):
-    """Batches of >= 64 leaves build leaf images of up to 160 KB in LDS (1024-thread
-    workgroups above 32 KB; TurtleKV leaves of small items reach ~80K keys): a 100000-key leaf
-    (125 KB at 10 bits/key, 150 KB at 12) and a 40000-key one among small leaves; at 14 bits/key
-    the 100000-key leaf (175 KB) sends the batch to the window path (two windows)."""
+    """Batches of >= 64 leaves build leaf images of up to 160 KB in LDS (TurtleKV leaves of
+    small items reach ~80K keys): a 100000-key leaf (125 KB at 10 bits/key, 150 KB at 12) and a
+    40000-key one among small leaves -- 70 leaves of 3,000 keys on average, so the split build,
+    two workgroups per leaf; at 14 bits/key the 100000-key leaf (175 KB) sends the batch to the
+    window path (two windows)."""
     rng = np.random.default_rng(77)
     counts = [int(c) for c in rng.integers(0, 2000, 70)]
     counts[5], counts[40], counts[69] = 100000, 40000, 0
@@ -716,6 +717,11 @@ def test_bloom_big_leaves_in_lds(oracle, amq, torch, shape):
         plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), counts, bpk,
                               offsets_t=None if offs is None else torch.from_numpy(offs).cuda())
         assert (plan.max_seg_blocks * 64 > 160 * 1024) == (bpk == 14)
+        r, _ = amq.filters.build_route(plan, stride, offs is not None)
+        if bpk == 14:
+            assert r.route == amq.abi.ROUTE_WINDOW and r.windows == 2
+        else:
+            assert r.route == amq.abi.ROUTE_SPLIT and r.parts == 2 and r.lds_bytes == 64 * plan.max_seg_blocks
         assert_same(plan, out, ref)
 
 
@@ -723,21 +729,28 @@ def test_bloom_big_leaves_in_lds(oracle, amq, torch, shape):
 def test_bloom_oversize_leaf_in_batch(oracle, amq, torch, big):
     """A multi-leaf batch holding a leaf beyond the LDS budget: a 175 KB image takes the
     window path (partial images in the workspace, merged); a 3.75 MB one (24 windows, more
-    than the window path's 16) the tiled monolithic build of its own (tkv_amq_build_ex), the
+    than the window path's 16) the tiled build in a multi-leaf launch (tkv_amq_build_ex), the
     other leaves the batch kernels from a compacted leaf list."""
     counts = [big, 500, 16384]
     keys = oracle.gen_keys16(15, 0, sum(counts))
     ref = oracle_per_segment(oracle, 0, keys, counts, 10)
     plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), counts, 10)
     assert plan.workspace_bytes > 0
+    r, leaves = amq.filters.build_route(plan)
+    if big == 140000:
+        assert r.route == amq.abi.ROUTE_WINDOW and r.parts > 1 and not any(leaves)
+    else:
+        assert list(leaves) == [amq.abi.LEAF_MULTI, amq.abi.LEAF_BATCH, amq.abi.LEAF_BATCH]
+        assert r.route == amq.abi.ROUTE_SPLIT   # (the compacted 500- and 16384-key leaves)
     assert_same(plan, out, ref)
 
 
 @pytest.mark.parametrize("shape", ["k16", "k24", "var"])
 def test_bloom_oversize_leaves_among_many(oracle, amq, torch, shape):
     """Several oversize leaves (past 16 windows) at the start, middle and end of a batch of
-    small and window-sized leaves, 16- and 24-byte keys (the monolithic build, one leaf at a
-    time) and variable-length keys (those leaves with device atomics, the rest batched)."""
+    small and window-sized leaves, 16- and 24-byte keys (the tiled build, the three leaves in
+    one multi-leaf launch) and variable-length keys (those leaves hashed into bit records and
+    tiled one at a time), the rest batched (the window path: a 150,000-key leaf is among them)."""
     rng = np.random.default_rng(3)
     counts = [2_600_000] + [int(c) for c in rng.integers(0, 20000, 70)] + [3_100_000, 150_000] + \
              [int(c) for c in rng.integers(0, 3000, 30)] + [2_300_001]
@@ -756,6 +769,11 @@ def test_bloom_oversize_leaves_among_many(oracle, amq, torch, shape):
                              offsets=None if offs is None else offs.astype(np.uint64))
     plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), counts, 10,
                           offsets_t=None if offs is None else torch.from_numpy(offs).cuda())
+    r, leaves = amq.filters.build_route(plan, stride, offs is not None)
+    big = amq.abi.LEAF_TILED_RECORDS if shape == "var" else amq.abi.LEAF_MULTI
+    assert [i for i, x in enumerate(leaves) if x == big] == [0, 71, len(counts) - 1]
+    assert sum(x == amq.abi.LEAF_BATCH for x in leaves) == len(counts) - 3
+    assert r.route == amq.abi.ROUTE_WINDOW and r.windows == 2
     assert_same(plan, out, ref)
 
 
@@ -764,7 +782,7 @@ def test_bloom_oversize_leaves_among_many(oracle, amq, torch, shape):
     ("var", 12, [16384, 2_700_000, 0, 1, 2_900_000, 77]),
     ("k20", 10, [3_000_000, 500, 16384]),          # a fixed stride other than 16 and 24
     ("k40", 8, [5_200_000, 3]),                    # keys of 32 bytes and more: hashed per seed
-    ("var", 16, [3_000_000, 500]),                 # k > 8: device atomics (records hold 8 bits)
+    ("var", 16, [3_000_000, 500]),                 # k = 11: two records per key
     ("var", 10, [2_700_000]),                      # one filter past the window path
     ("k20", 12, [2_200_000]),
 ])
@@ -789,6 +807,11 @@ def test_bloom_oversize_other_key_shapes(oracle, amq, torch, shape, bpk, counts)
     plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), counts, bpk,
                           offsets_t=None if offs is None else torch.from_numpy(offs).cuda())
     assert plan.max_seg_blocks > 16 * 160 * 1024 // 64
+    r, leaves = amq.filters.build_route(plan, stride, offs is not None)
+    if len(counts) == 1:
+        assert r.route == amq.abi.ROUTE_TILED_RECORDS
+    else:
+        assert [x == amq.abi.LEAF_TILED_RECORDS for x in leaves] == [c > 2_000_000 for c in counts]
     assert_same(plan, out, ref)
 
 

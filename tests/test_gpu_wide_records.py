@@ -282,6 +282,9 @@ def test_oversize_other_shapes_above_12_bits(oracle, amq, torch, shape, bpk, cou
     assert plan.max_seg_blocks > 40960
     if bpk <= 23:
         assert plan.workspace_bytes >= 2 * 12 * counts[0]
+    _, leaves = amq.filters.build_route(plan, stride, offs is not None)
+    want = amq.abi.LEAF_TILED_RECORDS if bpk <= 23 else amq.abi.LEAF_ATOMICS
+    assert list(leaves) == [want] + [amq.abi.LEAF_BATCH] * (len(counts) - 1)
     kb = _batch(amq, torch, keys, offs)
     out = torch.full((plan.total_out_bytes,), 0xA5, dtype=torch.uint8, device="cuda")
     amq.build_all_filters(plan, kb, out=out)
@@ -290,6 +293,8 @@ def test_oversize_other_shapes_above_12_bits(oracle, amq, torch, shape, bpk, cou
     if bpk != 13:
         return
     # a workspace 256 bytes short of the plan's: the library falls back and still builds it
+    _, leaves = amq.filters.build_route(plan, stride, True, workspace_bytes=plan.workspace_bytes - 256)
+    assert leaves[0] == amq.abi.LEAF_ATOMICS
     ws = torch.full((plan.workspace_bytes,), 0xFF, dtype=torch.uint8, device="cuda")
     out2 = torch.full((plan.total_out_bytes,), 0x5A, dtype=torch.uint8, device="cuda")
     st = amq.abi.lib().tkv_amq_build_ex(plan.kind, kb.data.data_ptr(), kb.offsets.data_ptr(), 0, n,

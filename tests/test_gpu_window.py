@@ -24,11 +24,21 @@ def windows(plan):
     return -(-int(plan.max_seg_blocks) * 64 // (160 * 1024))
 
 
+def routes(amq, plan, stride=16, var=False, **kw):
+    """(the batch's route, its leaves' routes) as tkv_amq_build_route reports them, the leaf
+    routes as letters: B in the batch, M multi-leaf tiled, K / R tiled alone from keys / from
+    records, A device atomics."""
+    r, leaves = amq.filters.build_route(plan, stride, var, **kw)
+    return r, "".join("BMKRA-"[x] for x in leaves)
+
+
 def test_verdict_batch_70_leaves_200k_keys_12bpk(oracle, amq, torch):
     counts = [200_000] * 70
     keys = oracle.gen_keys16(31, 0, sum(counts))
     plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), counts, 12)
     assert windows(plan) == 2 and plan.workspace_bytes > 0   # two windows, partial images
+    r, _ = routes(amq, plan)
+    assert r.route == amq.abi.ROUTE_WINDOW and r.windows == 2 and r.parts > 1
     ref = oracle_per_segment(oracle, 0, keys, counts, 12)
     assert_same(plan, out, ref)
 
@@ -38,13 +48,18 @@ def test_verdict_batch_70_leaves_200k_keys_12bpk(oracle, amq, torch):
 def test_window_counts_and_hash_counts(oracle, amq, torch, big, bpk):
     """2, 4, 10 and 16 windows (2M keys at 10 bits/key: 2.5 MB), k = 3 / 7 / 8 / 11 / 22, a
     ragged mix of big, small, one-key and empty leaves in one batch (16-byte keys: the leaves
-    past 4 windows take the tiled build, the others the window path)."""
+    past 5 windows take the tiled build, the others the window path)."""
     rng = np.random.default_rng(big + bpk)
     counts = [int(c) for c in rng.integers(0, 3000, 12)]
     counts[0], counts[3], counts[7], counts[-1] = big, 1, 0, big // 3
     keys = oracle.gen_keys16(32, 0, sum(counts))
     plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), counts, bpk)
     assert 2 <= windows(plan) <= 16
+    blocks = [int(b) for b in plan.segs["n_blocks"]]
+    r, leaves = routes(amq, plan)
+    assert leaves == "".join("M" if b > 5 * 2560 else "B" for b in blocks)
+    if max(b for b in blocks if b <= 5 * 2560) > 2560:   # (else only small leaves are left)
+        assert r.route == amq.abi.ROUTE_WINDOW
     ref = oracle_per_segment(oracle, 0, keys, counts, bpk)
     assert_same(plan, out, ref)
 
@@ -65,6 +80,9 @@ def test_batch_tiled_past_five_windows(oracle, amq, torch, shape, bpk):
         keys, stride = rng.integers(0, 256, (n, 24), dtype=np.uint8), 24
     plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), counts, bpk)
     assert windows(plan) > 5
+    r, leaves = routes(amq, plan, stride)
+    assert leaves == "".join("M" if b > 5 * 2560 else "B" for b in plan.segs["n_blocks"])
+    assert r.route == amq.abi.ROUTE_WINDOW and r.windows == 5
     ref = oracle_per_segment(oracle, 0, keys, counts, bpk, stride=stride)
     assert_same(plan, out, ref)
 
@@ -83,6 +101,8 @@ def test_window_many_windows_variable_keys(oracle, amq, torch, big):
     plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), counts, 10,
                           offsets_t=torch.from_numpy(offs).cuda())
     assert 8 <= windows(plan) <= 16
+    r, leaves = routes(amq, plan, var=True)
+    assert r.route == amq.abi.ROUTE_WINDOW and r.windows == windows(plan) and leaves == "B" * len(counts)
     ref = oracle_per_segment(oracle, 0, keys, counts, 10, stride=0, offsets=offs.astype(np.uint64))
     assert_same(plan, out, ref)
 
@@ -107,6 +127,8 @@ def test_window_key_shapes(oracle, amq, torch, shape):
         plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), counts, bpk,
                               offsets_t=None if offs is None else torch.from_numpy(offs).cuda())
         assert windows(plan) >= 2
+        r, leaves = routes(amq, plan, stride, offs is not None)
+        assert r.route == amq.abi.ROUTE_WINDOW and r.windows == windows(plan) and leaves == "B" * len(counts)
         ref = oracle_per_segment(oracle, 0, keys, counts, bpk, stride=stride,
                                  offsets=None if offs is None else offs.astype(np.uint64))
         assert_same(plan, out, ref)
@@ -132,6 +154,11 @@ def test_window_one_filter(oracle, amq, torch, n, bpk, shape):
                               offsets_t=torch.from_numpy(offs).cuda())
         ref = oracle_per_segment(oracle, 0, keys, [n], bpk, stride=0, offsets=offs.astype(np.uint64))
     assert 2 <= windows(plan) <= 4
+    r, _ = routes(amq, plan, var=shape == "var")
+    if shape == "k16":
+        assert r.route == amq.abi.ROUTE_TILED_KEYS
+    else:
+        assert r.route == amq.abi.ROUTE_WINDOW and r.windows == windows(plan) and r.parts > 1
     assert_same(plan, out, ref)
 
 
@@ -143,6 +170,8 @@ def test_window_without_workspace_one_part(oracle, amq, torch):
     keys = oracle.gen_keys16(35, 0, sum(counts))
     plan = amq.plan_filters(0, counts, 10)
     assert plan.workspace_bytes > 0
+    r, _ = routes(amq, plan, workspace_bytes=0, ex=False)
+    assert r.route == amq.abi.ROUTE_WINDOW and r.parts == 1 and r.ws_bytes == 0
     kt = torch.from_numpy(keys).cuda()
     out = torch.zeros(plan.total_out_bytes, dtype=torch.uint8, device="cuda")
     amq.abi.check(amq.abi.lib().tkv_amq_build(0, _ptr(kt), None, 16, kt.shape[0],
@@ -205,6 +234,8 @@ def test_window_workspace_forms(oracle, amq, torch, form):
     assert P > 1 and plan.workspace_bytes == len(counts) * P * 64 * mb
     ws_bytes = {"parts": plan.workspace_bytes, "short_workspace": plan.workspace_bytes - 1,
                 "no_workspace": 0}[form]
+    r, _ = routes(amq, plan, workspace_bytes=ws_bytes, ex=False)
+    assert r.route == amq.abi.ROUTE_WINDOW and r.parts == (P if form == "parts" else 1)
     kt = torch.from_numpy(keys).cuda()
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device="cuda")
     out = torch.zeros(plan.total_out_bytes, dtype=torch.uint8, device="cuda")

@@ -95,7 +95,27 @@ EXPORTS = [
     "tkv_amq_bloom_route_records_any",
     "tkv_amq_path_probe_ws_bytes", "tkv_amq_path_probe",
     "tkv_amq_open_filters", "tkv_amq_scan_filters_ws_bytes", "tkv_amq_scan_filters",
+    "tkv_amq_build_route",
 ]
+
+# tkv_amq_build_route: TKV_AMQ_ROUTE_* (a Bloom batch's route, or a VQF batch's decide stage),
+# TKV_AMQ_PLACE_* (VQF place stage), TKV_AMQ_LEAF_* (tkv_amq_build_ex's leaves)
+ROUTE_SPLIT, ROUTE_WINDOW, ROUTE_LDS, ROUTE_TILED_KEYS, ROUTE_TILED_RECORDS, ROUTE_ATOMICS = range(6)
+ROUTE_VQF_BIG_U8, ROUTE_VQF_BIG_GLOBAL, ROUTE_VQF_RING_PLACE, ROUTE_VQF_RING_PLACE2, ROUTE_VQF_RING, \
+    ROUTE_VQF_DECIDE = range(16, 22)
+PLACE_NONE, PLACE_FUSED512, PLACE_FUSED256, PLACE_SCATTER = range(4)
+LEAF_BATCH, LEAF_MULTI, LEAF_TILED_KEYS, LEAF_TILED_RECORDS, LEAF_ATOMICS, LEAF_NONE = range(6)
+
+
+class BuildRoute(ctypes.Structure):
+    """struct tkv_amq_build_route (40 bytes)."""
+    _fields_ = [("route", ctypes.c_uint32), ("place", ctypes.c_uint32), ("parts", ctypes.c_uint32),
+                ("windows", ctypes.c_uint32), ("threads", ctypes.c_uint32),
+                ("located", ctypes.c_uint32), ("ws_bytes", ctypes.c_uint64),
+                ("lds_bytes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(BuildRoute) == 40
 
 # tkv_amq_open_filters' per-filter codes (TKV_AMQ_OPEN_*)
 OPEN_OK, OPEN_BAD_MAGIC, OPEN_WRONG_KIND, OPEN_BAD_GEOMETRY, OPEN_OUT_OF_BOUNDS, OPEN_MISALIGNED, \
@@ -262,6 +282,10 @@ def lib(build_if_missing: bool = True):
         L.tkv_amq_bloom_build_part_blocks.argtypes = [vp, u32, vp, prp, u32, vp, vp, u64, vp]
         L.tkv_amq_bloom_blocks_lost.restype = i32
         L.tkv_amq_bloom_blocks_lost.argtypes = [vp, u32, prp, vp]
+    if hasattr(L, "tkv_amq_build_route"):
+        L.tkv_amq_build_route.restype = i32
+        L.tkv_amq_build_route.argtypes = [i32, u32, i32, i32, u32, u64, u32, vp, i32, u64,
+                                          ctypes.POINTER(BuildRoute), vp]
     if hasattr(L, "tkv_amq_bloom_tile_blocks"):
         L.tkv_amq_bloom_tile_blocks.restype = u32
         L.tkv_amq_bloom_tile_blocks.argtypes = []

@@ -5178,6 +5178,72 @@ __global__ __launch_bounds__(1024) void bloom_compact_segs(const tkv_amq_segment
   }
 }
 
+// The runtime key shape as a compile-time constant: fn(std::integral_constant<int, MODE>).
+// with_key_mode: key_mode's three shapes (probes, hashes); with_build_key_mode: build_key_mode's
+// four (kKey24 besides).
+template <int M>
+using KeyModeC = std::integral_constant<int, M>;
+
+template <typename Fn>
+inline void with_key_mode(int mode, Fn&& fn)
+{
+  if (mode == kKey16) fn(KeyModeC<kKey16>{});
+  else if (mode == kKeyFixed) fn(KeyModeC<kKeyFixed>{});
+  else fn(KeyModeC<kKeyVar>{});
+}
+
+template <typename Fn>
+inline void with_build_key_mode(int bmode, Fn&& fn)
+{
+  if (bmode == kKey24) fn(KeyModeC<kKey24>{});
+  else with_key_mode(bmode, fn);
+}
+
+// the bit-record kernels' shapes: variable-length (offs) or a fixed stride, one record per key
+// or two (bloom_rpk)
+template <typename Fn>
+inline void with_any_shape(const uint64_t* offs, uint32_t rpk, Fn&& fn)
+{
+  if (offs && rpk == 2) fn(KeyModeC<kKeyVar>{}, KeyModeC<2>{});
+  else if (offs) fn(KeyModeC<kKeyVar>{}, KeyModeC<1>{});
+  else if (rpk == 2) fn(KeyModeC<kKeyFixed>{}, KeyModeC<2>{});
+  else fn(KeyModeC<kKeyFixed>{}, KeyModeC<1>{});
+}
+
+// a launch with or without probe options (the kernels' kOpts)
+template <typename Fn>
+inline void with_flag(bool on, Fn&& fn)
+{
+  if (on) fn(std::true_type{});
+  else fn(std::false_type{});
+}
+
+// Kernel attributes (dynamic LDS above 64 KiB) are set once per device: a process may drive
+// several GPUs from different threads.
+constexpr int kMaxDevices = 64;
+template <typename Fn>
+inline void once_per_device(std::once_flag (&flags)[kMaxDevices], Fn&& fn)
+{
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) {
+    fn();
+    return;
+  }
+  std::call_once(flags[dev], fn);
+}
+
+// Kernel K with its dynamic LDS limit raised to `cap` bytes first (one flag array per kernel
+// instantiation, so a launch site names the kernel once and no list of instantiations is kept).
+template <auto K, typename... A>
+inline void launch_lds_cap(uint32_t cap, dim3 grid, dim3 block, size_t lds, hipStream_t s, A&&... a)
+{
+  static std::once_flag flags[kMaxDevices];
+  once_per_device(flags, [cap] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+  });
+  hipLaunchKernelGGL(K, grid, block, lds, s, std::forward<A>(a)...);
+}
+
 constexpr uint32_t kBloomLdsBudget = 64 * 1024;  // dynamic LDS a launch gets without the attribute
 // Leaf images are built in LDS up to the whole CU's LDS (a 160 KB image: 1.3M bits, ~130K
 // keys at 10 bits/key; TurtleKV leaves of small items reach ~80K keys): one workgroup per
@@ -5261,33 +5327,26 @@ inline uint32_t bloom_window_parts(uint32_t n_segs, uint64_t n_keys, uint64_t ma
   return best;
 }
 
-// a batch the window path takes (n_keys: the batch's keys; mono16: one filter of 16-byte keys)
-inline bool bloom_window_path(uint32_t n_segs, uint64_t max_blocks, bool mono16)
-{
-  const uint32_t W = bloom_window_count(max_blocks);
-  if (W < 2 || W > kWinMaxWindows) return false;
-  return !(n_segs == 1 && mono16 && W > kWinMonoMax);
-}
-
+// one workgroup of NT threads per leaf, its image in LDS (bmode: build_key_mode)
 template <uint32_t NT>
-void launch_bloom_lds(int bmode, int mode, uint32_t n_segs, size_t lds, hipStream_t s,
-                      const uint8_t* keys, const uint64_t* offs, uint32_t stride,
-                      const tkv_amq_segment* d_segs, uint8_t* d_out)
+void launch_bloom_lds(int bmode, uint32_t n_segs, size_t lds, hipStream_t s, const uint8_t* keys,
+                      const uint64_t* offs, uint32_t stride, const tkv_amq_segment* d_segs, uint8_t* d_out)
 {
-  const dim3 grid(n_segs), block(NT);
-  if (bmode == kKey24)
-    hipLaunchKernelGGL((bloom_build_lds<kKey24, NT>), grid, block, lds, s, keys, offs, stride, d_segs, d_out, 0u);
-  else if (mode == kKey16)
-    hipLaunchKernelGGL((bloom_build_lds<kKey16, NT>), grid, block, lds, s, keys, offs, stride, d_segs, d_out, 0u);
-  else if (mode == kKeyFixed)
-    hipLaunchKernelGGL((bloom_build_lds<kKeyFixed, NT>), grid, block, lds, s, keys, offs, stride, d_segs, d_out, 0u);
-  else {
-    // variable-length keys sorted by length per chunk when the scratch fits beside the image
-    const size_t aux = 4ull * kVarAuxWords<NT>;
-    const uint32_t sort = lds + aux <= kBloomLeafLdsBudget ? 1u : 0u;
-    hipLaunchKernelGGL((bloom_build_lds<kKeyVar, NT>), grid, block, lds + (sort ? aux : 0), s, keys, offs,
-                       stride, d_segs, d_out, sort);
-  }
+  with_build_key_mode(bmode, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    // variable-length keys sorted by length per chunk when the scratch (kVarAuxWords) fits
+    // beside the image
+    const size_t aux = MODE == kKeyVar ? 4ull * kVarAuxWords<NT> : 0;
+    const uint32_t sort = aux && lds + aux <= kBloomLeafLdsBudget ? 1u : 0u;
+    const size_t bytes = lds + (sort ? aux : 0);
+    const dim3 grid(n_segs), block(NT);
+    // (256-thread workgroups build images of at most kBloomWideLds)
+    if (NT == 1024 && bytes > kBloomLdsBudget)
+      launch_lds_cap<&bloom_build_lds<MODE, 1024>>(kBloomLeafLdsBudget, grid, block, bytes, s, keys, offs, stride,
+                                                   d_segs, d_out, sort);
+    else
+      hipLaunchKernelGGL((bloom_build_lds<MODE, NT>), grid, block, bytes, s, keys, offs, stride, d_segs, d_out, sort);
+  });
 }
 
 inline uint32_t vqf_slots(int t) { return t == 8 ? 48u : 28u; }
@@ -5299,17 +5358,24 @@ uint32_t bloom_hash_count(uint32_t bpk)
   return k < 1 ? 1 : (k > kMaxBloomHashes ? kMaxBloomHashes : k);
 }
 
-inline int key_mode(const uint64_t* offs, uint32_t stride)
+inline int key_mode_of(bool var, uint32_t stride)
 {
-  if (offs) return kKeyVar;
+  if (var) return kKeyVar;
   return stride == 16 ? kKey16 : kKeyFixed;
 }
 
-// the Bloom build additionally has a 24-byte fast path (needs 8-byte aligned keys)
+inline int key_mode(const uint64_t* offs, uint32_t stride) { return key_mode_of(offs != nullptr, stride); }
+
+// the builds additionally have a 24-byte fast path (needs 8-byte aligned keys)
+inline int build_key_mode_of(bool var, uint32_t stride, bool aligned8)
+{
+  if (!var && stride == 24 && aligned8) return kKey24;
+  return key_mode_of(var, stride);
+}
+
 inline int build_key_mode(const uint8_t* keys, const uint64_t* offs, uint32_t stride)
 {
-  if (!offs && stride == 24 && (reinterpret_cast<uintptr_t>(keys) & 7) == 0) return kKey24;
-  return key_mode(offs, stride);
+  return build_key_mode_of(offs != nullptr, stride, (reinterpret_cast<uintptr_t>(keys) & 7) == 0);
 }
 
 inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
@@ -5334,35 +5400,8 @@ inline uint32_t probe_grid(uint64_t n, bool ex)
   return (uint32_t)(g < cap ? g : cap);
 }
 
-
-// Kernel attributes (dynamic LDS above 64 KiB) are set once per device: a process may drive
-// several GPUs from different threads.
-constexpr int kMaxDevices = 64;
-template <typename Fn>
-inline void once_per_device(std::once_flag (&flags)[kMaxDevices], Fn&& fn)
-{
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) {
-    fn();
-    return;
-  }
-  std::call_once(flags[dev], fn);
-}
-
-// Kernel attributes of the monolithic build (dynamic LDS above 64 KiB).
-inline void set_mono_attributes()
-{
-  static std::once_flag lds_attr[kMaxDevices];
-  once_per_device(lds_attr, [] {
-    for (const void* f : {reinterpret_cast<const void*>(&bloom_part_keys16),
-                          reinterpret_cast<const void*>(&bloom_part_keys24),
-                          reinterpret_cast<const void*>(&bloom_part_routed)})
-      (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(160 * 1024));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bloom_tile),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * kTileBlocks));
-  });
-}
+// the tiled builds' LDS limits: the partition kernels' and a tile's image
+constexpr uint32_t kPartLdsCap = 160 * 1024, kTileLdsCap = 64 * kTileBlocks;
 
 inline uint32_t filter_tiles(uint64_t n_blocks) { return (uint32_t)div_up(n_blocks, kTileBlocks); }
 
@@ -5373,17 +5412,16 @@ inline uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
 inline void launch_part_build(int src, PartArgs a, hipStream_t s, const tkv_amq_segment* d_segs,
                               uint8_t* d_out, uint32_t hdr_always)
 {
-  set_mono_attributes();
   a.src_kind = (uint32_t)src;
   a.tbl = part_tbl_fits(a.g.n_tiles) ? 1u : 0u;
   const size_t lds = a.tbl ? part_tbl_lds_bytes(a.g.n_tiles) : part_lds_bytes(a.g.n_tiles);
   const dim3 grid(a.g.P), block(kPartThreads);
-  if (src == kSrcKey24) hipLaunchKernelGGL(bloom_part_keys24, grid, block, lds, s, d_segs, a);
-  else if (src == kSrcKey16) hipLaunchKernelGGL(bloom_part_keys16, grid, block, lds, s, d_segs, a);
-  else hipLaunchKernelGGL(bloom_part_routed, grid, block, lds, s, d_segs, a);
+  if (src == kSrcKey24) launch_lds_cap<&bloom_part_keys24>(kPartLdsCap, grid, block, lds, s, d_segs, a);
+  else if (src == kSrcKey16) launch_lds_cap<&bloom_part_keys16>(kPartLdsCap, grid, block, lds, s, d_segs, a);
+  else launch_lds_cap<&bloom_part_routed>(kPartLdsCap, grid, block, lds, s, d_segs, a);
   const uint32_t S = a.split > 1 ? a.split : 1u;
-  hipLaunchKernelGGL(bloom_tile, dim3(a.g.n_tiles * S), dim3(kTileThreads), 64ull * kTileBlocks, s, d_segs, a,
-                     d_out, hdr_always);
+  launch_lds_cap<&bloom_tile>(kTileLdsCap, dim3(a.g.n_tiles * S), dim3(kTileThreads), 64ull * kTileBlocks, s, d_segs,
+                              a, d_out, hdr_always);
   if (S > 1) hipLaunchKernelGGL(bloom_tile_merge, dim3(a.g.n_tiles * kMergeChunks), dim3(256), 0, s, d_segs, a, d_out);
   hipLaunchKernelGGL(bloom_overflow, dim3(a.g.P), dim3(256), 0, s, d_segs, a, d_out);
 }
@@ -5454,10 +5492,10 @@ inline void launch_route_any(const RouteGeom& g, hipStream_t s, const uint8_t* k
                              uint32_t stride, uint32_t n, const tkv_amq_segment* d_seg, uint32_t q, uint32_t rpk,
                              uint32_t* ws, uint32_t* out_recs)
 {
-  if (offs && rpk == 2) launch_route_any_as<kKeyVar, 2>(g, s, keys, offs, 0u, n, d_seg, q, ws, out_recs);
-  else if (offs) launch_route_any_as<kKeyVar, 1>(g, s, keys, offs, 0u, n, d_seg, q, ws, out_recs);
-  else if (rpk == 2) launch_route_any_as<kKeyFixed, 2>(g, s, keys, nullptr, stride, n, d_seg, q, ws, out_recs);
-  else launch_route_any_as<kKeyFixed, 1>(g, s, keys, nullptr, stride, n, d_seg, q, ws, out_recs);
+  with_any_shape(offs, rpk, [&](auto M, auto R) {
+    launch_route_any_as<decltype(M)::value, decltype(R)::value>(g, s, keys, offs, offs ? 0u : stride, n, d_seg, q, ws,
+                                                                out_recs);
+  });
 }
 
 // Tiles per routed part (a filter past kDirectMaxTiles): the fewer tiles a partition spreads
@@ -5572,21 +5610,6 @@ inline RouteBlock route_block(const tkv_amq_route_plan& rp, uint64_t jstride = 0
   return b;
 }
 
-inline void set_route_attributes()
-{
-  static std::once_flag attr[kMaxDevices];
-  once_per_device(attr, [] {
-    for (const void* f : {reinterpret_cast<const void*>(&bloom_route_part<8, 16>),
-                          reinterpret_cast<const void*>(&bloom_route_part<7, 16>),
-                          reinterpret_cast<const void*>(&bloom_route_part<0, 16>),
-                          reinterpret_cast<const void*>(&bloom_route_part<8, 24>),
-                          reinterpret_cast<const void*>(&bloom_route_part<0, 24>)})
-      (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)route_lds_bytes(kRouteMaxParts));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bloom_part_segs),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-  });
-}
-
 // the route of n keys (kb 16 or 24) into the part blocks at d_dst (part p at (p / world) *
 // jstride + (p % world) * block_bytes; jstride 0: world * block_bytes) (from_seg: keys [0, n) of
 // the segment, n capped by its count -- tkv_amq_build's plan; else exactly n keys)
@@ -5618,14 +5641,14 @@ inline PartArgs route_args(const tkv_amq_route_plan& rp, const uint8_t* keys, ui
 inline void launch_route_blocks(const PartArgs& a, const tkv_amq_route_plan& rp, hipStream_t s,
                                 const tkv_amq_segment* d_seg, bool pack)
 {
-  set_route_attributes();
   const dim3 g(rp.route_wgs), b(kPartThreads);
   const size_t lds = route_lds_bytes(rp.n_parts);
-  if (a.kb == 24 && rp.hash_count == 8) hipLaunchKernelGGL((bloom_route_part<8, 24>), g, b, lds, s, d_seg, a);
-  else if (a.kb == 24) hipLaunchKernelGGL((bloom_route_part<0, 24>), g, b, lds, s, d_seg, a);
-  else if (rp.hash_count == 8) hipLaunchKernelGGL((bloom_route_part<8, 16>), g, b, lds, s, d_seg, a);
-  else if (rp.hash_count == 7) hipLaunchKernelGGL((bloom_route_part<7, 16>), g, b, lds, s, d_seg, a);
-  else hipLaunchKernelGGL((bloom_route_part<0, 16>), g, b, lds, s, d_seg, a);
+  constexpr uint32_t cap = route_lds_bytes(kRouteMaxParts);
+  if (a.kb == 24 && rp.hash_count == 8) launch_lds_cap<&bloom_route_part<8, 24>>(cap, g, b, lds, s, d_seg, a);
+  else if (a.kb == 24) launch_lds_cap<&bloom_route_part<0, 24>>(cap, g, b, lds, s, d_seg, a);
+  else if (rp.hash_count == 8) launch_lds_cap<&bloom_route_part<8, 16>>(cap, g, b, lds, s, d_seg, a);
+  else if (rp.hash_count == 7) launch_lds_cap<&bloom_route_part<7, 16>>(cap, g, b, lds, s, d_seg, a);
+  else launch_lds_cap<&bloom_route_part<0, 16>>(cap, g, b, lds, s, d_seg, a);
   if (pack) hipLaunchKernelGGL(bloom_route_ovf_pack, dim3(rp.route_wgs), dim3(256), 0, s, a);
 }
 
@@ -5638,8 +5661,6 @@ inline void launch_part_from_blocks(const tkv_amq_route_plan& rp, hipStream_t s,
   const uint32_t t0 = p * rp.part_tiles;
   if (t0 >= rp.n_tiles) return;
   const uint32_t tn = std::min(rp.part_tiles, rp.n_tiles - t0);
-  set_mono_attributes();
-  set_route_attributes();
   PartArgs a{};
   a.src = d_recv;
   a.tile0 = t0;
@@ -5651,9 +5672,9 @@ inline void launch_part_from_blocks(const tkv_amq_route_plan& rp, hipStream_t s,
   a.n_src_segs = n_recv;
   a.seg_part = 0;
   a.tbl = part_tbl_fits(tn) ? 1u : 0u;
-  hipLaunchKernelGGL(bloom_part_segs, dim3(a.g.P), dim3(kPartThreads),
-                     a.tbl ? part_tbl_lds_bytes(tn) : part_lds_bytes(tn), s, d_seg, a);
-  hipLaunchKernelGGL(bloom_tile, dim3(tn), dim3(kTileThreads), 64ull * kTileBlocks, s, d_seg, a, d_out, 1u);
+  launch_lds_cap<&bloom_part_segs>(kPartLdsCap, dim3(a.g.P), dim3(kPartThreads),
+                                   a.tbl ? part_tbl_lds_bytes(tn) : part_lds_bytes(tn), s, d_seg, a);
+  launch_lds_cap<&bloom_tile>(kTileLdsCap, dim3(tn), dim3(kTileThreads), 64ull * kTileBlocks, s, d_seg, a, d_out, 1u);
   hipLaunchKernelGGL(bloom_overflow, dim3(a.g.P), dim3(256), 0, s, d_seg, a, d_out);
 }
 
@@ -5759,16 +5780,11 @@ inline void launch_any(const AnyPlan& p, uint32_t k, hipStream_t s, const uint8_
   uint32_t* recs = reinterpret_cast<uint32_t*>(ws);
   const uint32_t g = (uint32_t)div_up(n, 256), rpk = bloom_rpk(k);
   const dim3 grid(g), block(256);
-  if (g) {
-    if (offs && rpk == 2)
-      hipLaunchKernelGGL((bloom_any_records<kKeyVar, 2>), grid, block, 0, s, keys, offs, 0u, d_seg, n, recs);
-    else if (offs)
-      hipLaunchKernelGGL((bloom_any_records<kKeyVar, 1>), grid, block, 0, s, keys, offs, 0u, d_seg, n, recs);
-    else if (rpk == 2)
-      hipLaunchKernelGGL((bloom_any_records<kKeyFixed, 2>), grid, block, 0, s, keys, offs, stride, d_seg, n, recs);
-    else
-      hipLaunchKernelGGL((bloom_any_records<kKeyFixed, 1>), grid, block, 0, s, keys, offs, stride, d_seg, n, recs);
-  }
+  if (g)
+    with_any_shape(offs, rpk, [&](auto M, auto R) {
+      hipLaunchKernelGGL((bloom_any_records<decltype(M)::value, decltype(R)::value>), grid, block, 0, s, keys, offs,
+                         offs ? 0u : stride, d_seg, n, recs);
+    });
   PartArgs a{reinterpret_cast<const uint8_t*>(recs), rpk * n, 0u, 0u, 16u, nullptr, 0u, ws + p.part_off, p.pg};
   a.split = p.split;
   a.part_img = ws + p.img_off;
@@ -5812,11 +5828,108 @@ inline void launch_mono(const MonoPlan& m, hipStream_t s, const uint8_t* keys, u
   }
 }
 
-// a one-filter Bloom batch too large for one LDS image takes the monolithic build (it needs a
-// workspace of mono_plan(n_keys, n_blocks).bytes and 16- or 24-byte keys)
-inline bool bloom_partitioned(uint32_t n_segs, uint64_t max_blocks, uint64_t n_keys)
+// The route of a Bloom batch ("Build routes"), in the order bloom_route tries them.
+enum class BloomRoute : uint32_t { Split = TKV_AMQ_ROUTE_SPLIT, Window, Lds, TiledKeys, TiledRecords, Atomics };
+static_assert((uint32_t)BloomRoute::Atomics == TKV_AMQ_ROUTE_ATOMICS, "TKV_AMQ_ROUTE_* (tkv_amq.h) in this order");
+
+struct BloomPlan {
+  BloomRoute route;
+  uint32_t parts;                   // Split: workgroups per leaf; Window: per (leaf, window)
+  uint32_t windows, window_blocks;  // Window
+  uint32_t threads;                 // the first kernel's workgroup size
+  uint32_t lds_bytes;               // a workgroup's LDS image (Split, Window, Lds)
+  uint64_t ws_bytes;                // the workspace the route uses (0: none)
+  MonoPlan mono;                    // TiledKeys
+  AnyPlan any;                      // TiledRecords
+};
+
+constexpr uint64_t kWsUnlimited = ~0ull;
+
+// The one place a Bloom batch's route is chosen: the builds launch what it returns, the plan
+// sizes the workspace from it.  n_keys: the keys the leaves hold; bmode: build_key_mode; k: the
+// hash count (it decides only between TiledRecords and Atomics); have_ws / ws_bytes: the
+// workspace the build was given (none: every route that needs one falls through).
+inline BloomPlan bloom_route(uint32_t n_segs, uint64_t n_keys, uint64_t max_blocks, int bmode, uint32_t k,
+                             bool have_ws, uint64_t ws_bytes)
 {
-  return n_segs == 1 && 64 * max_blocks > kBloomLeafLdsBudget && n_keys <= 0xffffffffull;
+  BloomPlan p{};
+  p.parts = 1;
+  const uint64_t lds = 64 * max_blocks;
+  // a small batch: each leaf's keys over `parts` workgroups, then their images ORed
+  const uint32_t parts = bloom_split_parts(n_segs, n_keys, max_blocks);
+  const uint64_t split_ws = bloom_split_ws_bytes(n_segs, parts, max_blocks);
+  if (parts > 1 && have_ws && ws_bytes >= split_ws) {
+    p.route = BloomRoute::Split;
+    p.parts = parts;
+    p.threads = kSplitThreads;
+    p.lds_bytes = (uint32_t)lds;
+    p.ws_bytes = split_ws;
+    return p;
+  }
+  // One filter too large for one LDS image: 16- and 24-byte keys take the tiled build from the
+  // keys (each key hashed once) with a workspace of mono_plan's bytes.  Beyond kDirectMaxTiles
+  // tiles 24-byte keys travel as bit records only, which takes the one-pass route (mono.blocks:
+  // k known -- bloom_k_of 0 means the plan does not match n_keys -- and at most 8; the bits
+  // past eight would be set from the keys, which the route does not carry).
+  const bool one = n_segs == 1 && lds > kBloomLeafLdsBudget && n_keys <= 0xffffffffull && have_ws;
+  if (one) p.mono = mono_plan(n_keys, max_blocks);
+  const bool tiled_keys = one && ws_bytes >= p.mono.bytes &&
+                          (bmode == kKey16 || (bmode == kKey24 && (p.mono.g == 1 || p.mono.blocks)));
+  // leaves beyond one CU's LDS, up to kWinMaxWindows windows of it (one filter the tiled build
+  // takes: up to kWinMonoMax)
+  const uint32_t W = bloom_window_count(max_blocks);
+  if (W >= 2 && W <= kWinMaxWindows && !(tiled_keys && W > kWinMonoMax)) {
+    p.route = BloomRoute::Window;
+    p.windows = W;
+    p.window_blocks = bloom_window_blocks(max_blocks);
+    p.threads = kWinThreads;
+    p.lds_bytes = 64 * p.window_blocks;
+    p.parts = bloom_window_parts(n_segs, n_keys, max_blocks);
+    p.ws_bytes = bloom_split_ws_bytes(n_segs, p.parts, max_blocks);
+    if (p.parts > 1 && (!have_ws || ws_bytes < p.ws_bytes)) {
+      p.parts = 1;  // no workspace for partial images: one part per leaf, no merge
+      p.ws_bytes = 0;
+    }
+    return p;
+  }
+  if (lds <= kBloomLeafLdsBudget && n_segs >= kBloomSpreadSegs) {
+    p.route = BloomRoute::Lds;
+    p.threads = n_segs < kBloomWideSegs || lds > kBloomWideLds ? 1024u : 256u;
+    p.lds_bytes = (uint32_t)lds;
+    return p;
+  }
+  if (tiled_keys) {
+    p.route = BloomRoute::TiledKeys;
+    p.threads = kPartThreads;
+    p.ws_bytes = p.mono.bytes;
+    return p;
+  }
+  // one filter of variable-length or other fixed-size keys: the same, from bit records
+  if (one && bmode != kKey16 && bmode != kKey24 && any_tiled_ok(k, n_keys, max_blocks)) {
+    p.any = any_plan(k, n_keys, max_blocks);
+    if (ws_bytes >= p.any.bytes) {
+      p.route = BloomRoute::TiledRecords;
+      p.threads = 256;
+      p.ws_bytes = p.any.bytes;
+      return p;
+    }
+  }
+  // fewer than kBloomSpreadSegs leaves, leaves beyond the LDS budget in a multi-leaf batch, or
+  // one filter the tiled builds do not take (no room, k > 16, or 24-byte keys with k > 8 beyond
+  // kDirectMaxTiles tiles): device atomics
+  p.route = BloomRoute::Atomics;
+  p.threads = 256;
+  return p;
+}
+
+// the largest workspace bloom_route can use for the batch over the key shapes in `bmodes`
+inline uint64_t bloom_route_ws_bytes(uint32_t n_segs, uint64_t n_keys, uint64_t max_blocks, uint32_t k,
+                                     std::initializer_list<int> bmodes)
+{
+  uint64_t need = 0;
+  for (const int bmode : bmodes)
+    need = std::max(need, bloom_route(n_segs, n_keys, max_blocks, bmode, k, true, kWsUnlimited).ws_bytes);
+  return need;
 }
 
 // A Bloom batch with leaves of more than kWinMaxWindows windows (images past 2.5 MB) among
@@ -5835,11 +5948,23 @@ constexpr uint32_t kBatchMonoWindows = 5;
 inline uint32_t batch_window_max(bool fixed) { return fixed ? kBatchMonoWindows : kWinMaxWindows; }
 inline bool batch_tiled(uint64_t n_blocks, bool fixed) { return bloom_window_count(n_blocks) > batch_window_max(fixed); }
 
-inline uint64_t bloom_batch_ws_bytes(uint32_t n_segs, uint64_t n_keys, uint64_t max_blocks)
+// a batch tkv_amq_build_ex takes apart (fixed false: the test for any key shape)
+inline bool batch_has_tiled(uint32_t n_segs, uint64_t max_blocks, bool fixed)
 {
-  if (bloom_window_path(n_segs, max_blocks, false))
-    return bloom_split_ws_bytes(n_segs, bloom_window_parts(n_segs, n_keys, max_blocks), max_blocks);
-  return bloom_split_ws_bytes(n_segs, bloom_split_parts(n_segs, n_keys, max_blocks), max_blocks);
+  return n_segs >= 2 && batch_tiled(max_blocks, fixed);
+}
+
+// One tiled leaf of such a batch that no multi-leaf launch takes: built alone from its keys
+// or from bit records, else with device atomics (the batch kernels are not launched per leaf).
+inline BloomPlan bloom_leaf_route(const tkv_amq_segment& g, int bmode, bool have_ws, uint64_t ws_bytes)
+{
+  const BloomPlan p = bloom_route(1, g.n_keys, g.n_blocks, bmode, g.hash_count, have_ws, ws_bytes);
+  if (p.route == BloomRoute::TiledKeys || p.route == BloomRoute::TiledRecords) return p;
+  BloomPlan a{};
+  a.route = BloomRoute::Atomics;
+  a.parts = 1;
+  a.threads = 256;
+  return a;
 }
 
 // A tiled leaf of at most kDirectMaxTiles tiles joins a multi-leaf launch (bloom_part_multi).
@@ -5903,19 +6028,11 @@ inline void multi_split(MultiParts& m, uint32_t n_tiles, uint8_t* split_img)
 inline void launch_multi(const MultiParts& m, uint32_t kb, uint32_t n_wgs, uint32_t n_tiles, size_t lds, hipStream_t s,
                          const tkv_amq_segment* d_segs, uint8_t* d_out)
 {
-  static std::once_flag attr[kMaxDevices];
-  once_per_device(attr, [] {
-    for (const void* f : {reinterpret_cast<const void*>(&bloom_part_multi16),
-                          reinterpret_cast<const void*>(&bloom_part_multi24)})
-      (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bloom_tile_multi),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * kTileBlocks));
-  });
-  if (kb == 24) hipLaunchKernelGGL(bloom_part_multi24, dim3(n_wgs), dim3(kPartThreads), lds, s, d_segs, m);
-  else hipLaunchKernelGGL(bloom_part_multi16, dim3(n_wgs), dim3(kPartThreads), lds, s, d_segs, m);
+  if (kb == 24) launch_lds_cap<&bloom_part_multi24>(kPartLdsCap, dim3(n_wgs), dim3(kPartThreads), lds, s, d_segs, m);
+  else launch_lds_cap<&bloom_part_multi16>(kPartLdsCap, dim3(n_wgs), dim3(kPartThreads), lds, s, d_segs, m);
   const uint32_t S = m.n ? (m.l[0].split > 1 ? m.l[0].split : 1u) : 1u;
-  hipLaunchKernelGGL(bloom_tile_multi, dim3(n_tiles * S), dim3(kTileThreads), 64ull * kTileBlocks, s, d_segs, m,
-                     d_out);
+  launch_lds_cap<&bloom_tile_multi>(kTileLdsCap, dim3(n_tiles * S), dim3(kTileThreads), 64ull * kTileBlocks, s, d_segs,
+                                    m, d_out);
   if (S > 1)
     hipLaunchKernelGGL(bloom_tile_merge_multi, dim3(n_tiles * kMergeChunks), dim3(256), 0, s, d_segs, m, d_out);
   hipLaunchKernelGGL(bloom_overflow_multi, dim3(n_wgs), dim3(256), 0, s, d_segs, m, d_out);
@@ -5929,10 +6046,10 @@ inline void launch_multi(const MultiParts& m, uint32_t kb, uint32_t n_wgs, uint3
 inline uint64_t bloom_oversize_ws_bytes(const tkv_amq_segment* segs, uint32_t n_segs)
 {
   uint64_t need = 0;
+  const uint64_t wg_items = multi_wg_items(multi_keys_of(segs, n_segs));
   for (const bool fixed : {true, false}) {
     uint32_t n_small = 0;
     uint64_t small_keys = 0, small_max = 0, big = 0, multi_sum = 0, multi_max = 0;
-    const uint64_t wg_items = multi_wg_items(multi_keys_of(segs, n_segs));
     for (uint32_t i = 0; i < n_segs; ++i) {
       const tkv_amq_segment& g = segs[i];
       if (!batch_tiled(g.n_blocks, fixed)) {
@@ -5943,17 +6060,211 @@ inline uint64_t bloom_oversize_ws_bytes(const tkv_amq_segment* segs, uint32_t n_
         const uint64_t b = align256(multi_geom(g.n_keys, g.n_blocks, wg_items).bytes);
         multi_sum += b;
         multi_max = std::max(multi_max, b);
-      } else if (fixed) {
-        big = std::max(big, mono_plan(g.n_keys, g.n_blocks).bytes);
-      } else if (any_tiled_ok(g.hash_count, g.n_keys, g.n_blocks)) {
-        big = std::max(big, any_plan(g.hash_count, g.n_keys, g.n_blocks).bytes);  // (bloom_part_any)
+      } else {
+        for (const int bmode : {fixed ? kKey16 : kKeyFixed, fixed ? kKey24 : kKeyVar})
+          big = std::max(big, bloom_leaf_route(g, bmode, true, kWsUnlimited).ws_bytes);
       }
     }
-    const uint64_t small = n_small ? bloom_batch_ws_bytes(n_small, small_keys, small_max) : 0;
+    // (the compacted batch is sized for keys the tiled build does not take, whatever the batch's
+    // keys: a lone compacted leaf of 2..kBatchMonoWindows windows of 16- or 24-byte keys is built
+    // tiled when the rest of this workspace holds mono_plan's bytes, from windows otherwise)
+    const uint64_t small =
+        n_small ? bloom_route_ws_bytes(n_small, small_keys, small_max, 0, {kKeyFixed, kKeyVar}) : 0;
     const uint64_t multi = multi_sum ? std::min(multi_sum, std::max(multi_max, kMultiWsBudget)) + kSplitImgBytes : 0;
     need = std::max(need, std::max(std::max(small, big), multi));
   }
   return align256(64ull * n_segs) + need;
+}
+
+// How tkv_amq_build_ex builds leaf g of a batch (fixed: its keys are 16 or 24 bytes; wg_items:
+// multi_wg_items of the batch; rest_bytes: the workspace after the leaf list).
+struct LeafRoute {
+  uint32_t kind;   // TKV_AMQ_LEAF_*
+  PartGeom pg;     // TKV_AMQ_LEAF_MULTI: the leaf's share of a multi-leaf launch
+  BloomPlan plan;  // the leaves built alone
+};
+
+inline LeafRoute bloom_leaf(const tkv_amq_segment& g, bool fixed, int bmode, uint64_t wg_items, uint64_t rest_bytes)
+{
+  LeafRoute r{};
+  r.kind = TKV_AMQ_LEAF_BATCH;
+  if (!batch_tiled(g.n_blocks, fixed)) return r;
+  r.kind = TKV_AMQ_LEAF_NONE;
+  if (g.bits_per_key == 0) return r;
+  // the tiled leaves of at most kDirectMaxTiles tiles: multi-leaf launches (the group's partial
+  // tile images come first in the workspace, then the leaves' workspaces)
+  if (fixed && multi_leaf(g.n_keys, g.n_blocks)) {
+    r.pg = multi_geom(g.n_keys, g.n_blocks, wg_items);
+    r.kind = TKV_AMQ_LEAF_MULTI;
+    if (rest_bytes > kSplitImgBytes && align256(r.pg.bytes) <= rest_bytes - kSplitImgBytes) return r;
+  }
+  r.plan = bloom_leaf_route(g, bmode, true, rest_bytes);
+  r.kind = r.plan.route == BloomRoute::TiledKeys      ? TKV_AMQ_LEAF_TILED_KEYS
+           : r.plan.route == BloomRoute::TiledRecords ? TKV_AMQ_LEAF_TILED_RECORDS
+                                                      : TKV_AMQ_LEAF_ATOMICS;
+  return r;
+}
+
+// what every batch launch takes (mode: key_mode; bmode: build_key_mode)
+struct BuildArgs {
+  const uint8_t* keys; const uint64_t* offs; uint32_t stride; uint64_t n_keys;
+  const tkv_amq_segment* d_segs; uint32_t n_segs, max_blocks; uint8_t* d_out;
+  void* d_ws; uint64_t ws_bytes; hipStream_t s; int mode, bmode;
+};
+
+inline void launch_split_merge(const BuildArgs& b, uint32_t parts)
+{
+  const uint32_t chunks = (uint32_t)div_up(4ull * b.max_blocks, kMergeThreads);
+  hipLaunchKernelGGL(bloom_split_merge, dim3(b.n_segs * chunks), dim3(kMergeThreads), 0, b.s, b.d_segs, parts, chunks,
+                     static_cast<uint8_t*>(b.d_ws), 64ull * b.max_blocks, b.d_out);
+}
+
+inline void launch_bloom_split(const BuildArgs& b, const BloomPlan& p)
+{
+  with_build_key_mode(b.bmode, [&](auto M) {
+    launch_lds_cap<&bloom_build_split<decltype(M)::value>>(
+        kBloomLeafLdsBudget, dim3(b.n_segs * p.parts), dim3(kSplitThreads), 64ull * b.max_blocks, b.s, b.keys, b.offs,
+        b.stride, b.d_segs, p.parts, static_cast<uint8_t*>(b.d_ws), 64ull * b.max_blocks);
+  });
+  launch_split_merge(b, p.parts);
+}
+
+inline void launch_bloom_window(const BuildArgs& b, const BloomPlan& p)
+{
+  with_build_key_mode(b.bmode, [&](auto M) {
+    launch_lds_cap<&bloom_build_window<decltype(M)::value>>(
+        kBloomLeafLdsBudget, dim3(b.n_segs * p.windows * p.parts), dim3(kWinThreads), 64ull * p.window_blocks, b.s,
+        b.keys, b.offs, b.stride, b.d_segs, p.windows, p.window_blocks, p.parts, static_cast<uint8_t*>(b.d_ws),
+        64ull * b.max_blocks, b.d_out);
+  });
+  if (p.parts > 1) launch_split_merge(b, p.parts);
+}
+
+// keys [key0, key_end) of the key array into the n_segs leaves at d_segs, with device atomics
+inline void launch_bloom_atomics(hipStream_t s, int mode, const uint8_t* keys, const uint64_t* offs, uint32_t stride,
+                                 const tkv_amq_segment* d_segs, uint32_t n_segs, uint64_t key0, uint64_t key_end,
+                                 uint8_t* d_out)
+{
+  hipLaunchKernelGGL(bloom_global_init, dim3(n_segs), dim3(256), 0, s, d_segs, d_out);
+  const uint32_t g2 = (uint32_t)std::min<uint64_t>(div_up(key_end - key0, 256), 8192);
+  if (g2)
+    with_key_mode(mode, [&](auto M) {
+      hipLaunchKernelGGL(bloom_global_set<decltype(M)::value>, dim3(g2), dim3(256), 0, s, keys, offs, stride, d_segs,
+                         n_segs, key_end, d_out, key0);
+    });
+}
+
+// The stages of a VQF batch ("Build routes").
+// (vqf_decide_big<kCntU8 / kCntGlobal>, vqf_ring_place<kRingPlaceSlots / kRingPlace2Slots>, which
+// decide and place, vqf_decide_ring, vqf_decide; vqf_place_fused<512 / 256>, vqf_scatter + vqf_place)
+enum class VqfDecide : uint32_t { BigU8 = TKV_AMQ_ROUTE_VQF_BIG_U8, BigGlobal, RingPlace, RingPlace2, Ring, Decide };
+enum class VqfPlace : uint32_t { None = TKV_AMQ_PLACE_NONE, Fused512, Fused256, Scatter };
+static_assert((uint32_t)VqfDecide::Decide == TKV_AMQ_ROUTE_VQF_DECIDE && (uint32_t)VqfPlace::Scatter == TKV_AMQ_PLACE_SCATTER, "");
+
+struct VqfPlan {
+  VqfDecide decide;
+  VqfPlace place;
+  bool located;         // vqf_locate_keys first; the ring's producers read located records
+  size_t lds;           // vqf_decide, vqf_decide_big: the count table (+ the lane-mask table)
+  size_t rl;            // the ring kernels' LDS
+  uint32_t cw, tbl;     // vqf_ring_place: count words, match tables
+  int flags;            // vqf_decide, vqf_decide_ring: 1 lane-mask table, 2 compact records
+  uint32_t place_parts, place_span;  // workgroups per leaf of the place stage, blocks each
+  uint32_t key_wgs;     // the per-key kernels' grid (vqf_locate_keys, vqf_scatter); 0: no keys
+};
+
+// The one place a VQF batch's stages are chosen (vmode: build_key_mode).
+inline VqfPlan vqf_route(uint32_t n_segs, uint32_t max_blocks, int vmode, uint64_t n_keys)
+{
+  VqfPlan p{};
+  p.key_wgs = (uint32_t)div_up(n_keys, 256);
+  // LDS: u32 block counts (+ the u64 lane-mask table when every leaf is small enough)
+  // The lane-mask table costs 8 B of LDS per block in every decide wave, and wins even where
+  // it costs waves per CU: 6,104 leaves of 804 blocks 2.49 -> 2.14 ms (16 instead of 24 waves
+  // per CU), 2,048 of 1,961 blocks 3.03 -> 2.52 ms, against block-id ballots
+  const int match_lds = max_blocks <= kVqfMatchLdsBlocks;
+  // a leaf whose LDS image exceeds the budget is placed by up to kFusedMaxParts workgroups
+  p.place_parts = (uint32_t)div_up(max_blocks, kFusedLdsBudget / (4 * kFusedRegionWords));
+  p.place_span = (uint32_t)div_up(max_blocks, p.place_parts);
+  const bool fused = p.place_parts <= kFusedMaxParts;  // compact records are read only there
+  p.flags = match_lds | (fused ? 2 : 0);
+  // 512 threads for a batch that does not fill the chip (the ring-decide sizes) or leaves of
+  // more than 512 blocks: lone leaf 98 -> 95 us, 2,048 x 80K keys 2.51 -> 2.30 ms; 256 for a
+  // full batch of small leaves (0.709 vs 0.697 ms at 100M keys)
+  if (fused) {
+    p.place = n_segs <= kVqfRingMaxSegs || max_blocks > 512 ? VqfPlace::Fused512 : VqfPlace::Fused256;
+  } else {
+    // several workgroups per leaf for large leaves (each takes every parts-th group of
+    // kPlaceThreads blocks)
+    p.place = VqfPlace::Scatter;
+    p.place_parts = (uint32_t)std::min<uint64_t>(div_up(max_blocks, 4 * kPlaceThreads), 256);
+    p.place_span = 0;
+  }
+  // the count table: u32 in LDS up to kVqfMaxLdsBlocks, u8 in LDS up to kVqfU8LdsBlocks, else
+  // in the workspace's block records (VqfCountMode).  A leaf past the u32 count table:
+  // vqf_decide_big for the whole batch (fused place is out of reach for such a leaf, so the
+  // records are the 8-byte ones)
+  if (max_blocks > kVqfMaxLdsBlocks) {
+    const bool u8 = max_blocks <= kVqfU8LdsBlocks;
+    p.decide = u8 ? VqfDecide::BigU8 : VqfDecide::BigGlobal;
+    p.lds = u8 ? (size_t)((max_blocks + 15) & ~15u) : 16;
+    return p;
+  }
+  p.lds = 4ull * ((max_blocks + 1) & ~1u) + (match_lds ? 8ull * max_blocks : 0);
+  // the ring kernel for small batches of leaves its count table holds (a batch with a larger
+  // leaf takes vqf_decide: the one-wave body inside the ring kernel set its registers, and so
+  // its workgroups per CU, for every batch).  Keys other than 16 bytes are read where they are
+  // hashed, which puts their load latency on vqf_decide's serial chain: the ring kernel, whose
+  // producers hash off the chain, stays faster up to ~4,096 leaves for them (1,024 leaves of
+  // 24-byte keys 0.47 -> 0.29 ms, variable-length 0.66 -> 0.38 ms; at 6,104 leaves vqf_decide
+  // wins, 1.25 vs 1.45 ms)
+  // 24-byte keys (TurtleKV's default key size hint), 8-byte aligned, are loaded ahead of
+  // their hash like 16-byte ones
+  const bool prefetched = vmode == kKey16 || vmode == kKey24;
+  // decide and place in one workgroup per leaf (vqf_ring_place): no key records, one launch;
+  // up to 256 leaves one workgroup per CU (ring of kRingPlaceSlots, match tables), up to 512 two
+  const bool rp1 = n_segs <= kRingPlaceMaxSegs && max_blocks <= kRingPlaceMaxBlocks;
+  const bool rp2 = !rp1 && n_segs <= kRingPlace2MaxSegs && max_blocks <= kRingPlace2MaxBlocks;
+  if (rp1 || rp2) {
+    p.decide = rp1 ? VqfDecide::RingPlace : VqfDecide::RingPlace2;
+    p.place = VqfPlace::None;
+    p.cw = ring_place_cnt_words(max_blocks);
+    p.tbl = rp1 && max_blocks <= kRingTblBlocks;  // (ring_place_lds_bytes sizes them)
+    p.rl = rp1 ? ring_place_lds_bytes(max_blocks) : ring_place_lds_bytes(max_blocks, kRingPlace2Slots, false);
+    // keys read where they are hashed (other than 16 or 24 bytes: the producers, not the
+    // decider, set a lone leaf's time): every key hashed and located on the whole chip first
+    // (vqf_locate_keys), the ring's producers then read 8-byte located records
+    p.located = !prefetched && n_segs <= (vmode == kKeyVar ? kVqfLocMaxSegsVar : kVqfLocMaxSegsFixed);
+    return p;
+  }
+  if (n_segs <= (prefetched ? kVqfRingMaxSegs : kVqfRingMaxSegsOther) && max_blocks <= kRingMaxBlocks) {
+    p.decide = VqfDecide::Ring;
+    p.rl = p.lds > kRingLdsBytes ? p.lds : kRingLdsBytes;
+    return p;
+  }
+  p.decide = VqfDecide::Decide;
+  return p;
+}
+
+constexpr uint32_t kVqfLdsCap = 160 * 1024;  // the VQF decide kernels' LDS limit
+
+// vqf_ring_place with NS ring slots, after vqf_locate_keys for located keys (MODE: build_key_mode)
+template <int MODE, uint32_t NS>
+inline void launch_ring_place(const BuildArgs& b, const VqfPlan& p)
+{
+  const dim3 g(b.n_segs), blk(kRingThreads);
+  if constexpr (MODE == kKeyFixed || MODE == kKeyVar) {
+    if (p.located) {
+      if (p.key_wgs)
+        hipLaunchKernelGGL(vqf_locate_keys<MODE>, dim3(p.key_wgs), dim3(256), 0, b.s, b.keys, b.offs, b.stride, b.d_segs,
+                           b.d_ws, b.ws_bytes, b.n_segs, b.n_keys);
+      launch_lds_cap<&vqf_ring_place<kKeyLoc, NS>>(kVqfLdsCap, g, blk, p.rl, b.s, nullptr, nullptr, 0, b.d_segs, b.d_ws,
+                                                   b.ws_bytes, b.n_segs, b.d_out, p.cw, p.tbl);
+      return;
+    }
+  }
+  launch_lds_cap<&vqf_ring_place<MODE, NS>>(kVqfLdsCap, g, blk, p.rl, b.s, b.keys, b.offs, b.stride, b.d_segs, b.d_ws,
+                                            b.ws_bytes, b.n_segs, b.d_out, p.cw, p.tbl);
 }
 
 }  // namespace
@@ -6145,27 +6456,17 @@ int tkv_amq_plan(int kind, const uint64_t* counts, const uint64_t* src_ids, uint
     *ws_bytes = 0;
     if (kind == TKV_AMQ_VQF && bpk != 0)
       *ws_bytes = vqf_temp_offset(n_segs) + kVqfTempStride * block_base + 8 * key_begin + 64;
-    // (the window path for one 16- or 24-byte-key filter above kWinMonoMax windows is not
-    // taken: the monolithic workspace below; any other window batch, its partial images.  The
-    // plan does not know the key shape, so a single filter of kWinMonoMax+1 .. kWinMaxWindows
-    // windows gets the larger of the two: other key shapes take the window path with it)
-    const uint64_t win_ws =
-        kind == TKV_AMQ_BLOOM && bpk != 0 && bloom_window_path(n_segs, max_blocks, false)
-            ? bloom_split_ws_bytes(n_segs, bloom_window_parts(n_segs, key_begin, max_blocks), max_blocks)
-            : 0;
-    if (kind == TKV_AMQ_BLOOM && bpk != 0 && bloom_window_path(n_segs, max_blocks, true))
-      *ws_bytes = win_ws;
-    else if (kind == TKV_AMQ_BLOOM && bloom_partitioned(n_segs, max_blocks, key_begin))
-      // (the plan does not know the key shape: other shapes take bloom_any_records' records)
-      *ws_bytes = std::max<uint64_t>({mono_plan(key_begin, max_blocks).bytes, win_ws,
-                                      any_tiled_ok(segs[0].hash_count, key_begin, max_blocks)
-                                          ? any_plan(segs[0].hash_count, key_begin, max_blocks).bytes
-                                          : uint64_t{0}});
-    else if (kind == TKV_AMQ_BLOOM)
-      *ws_bytes = bloom_split_ws_bytes(n_segs, bloom_split_parts(n_segs, key_begin, max_blocks),
-                                       max_blocks);
-    if (kind == TKV_AMQ_BLOOM && bpk != 0 && n_segs > 1 && batch_tiled(max_blocks, true))
-      *ws_bytes = bloom_oversize_ws_bytes(segs, n_segs);
+    if (kind == TKV_AMQ_BLOOM && max_blocks != 0) {
+      // The plan does not know the key shape: the largest need of any (one filter of 2 ..
+      // kWinMaxWindows windows: the tiled build's for 16- and 24-byte keys, else partial images)
+      const uint32_t k = n_segs == 1 ? segs[0].hash_count : 0u;
+      *ws_bytes = bloom_route_ws_bytes(n_segs, key_begin, max_blocks, k, {kKey16, kKey24, kKeyFixed, kKeyVar});
+      // (kept from before the routes had one chooser: such a filter also reserves the record
+      // build's workspace, which no route of that size uses)
+      if (n_segs == 1 && 64ull * max_blocks > kBloomLeafLdsBudget && any_tiled_ok(k, key_begin, max_blocks))
+        *ws_bytes = std::max(*ws_bytes, any_plan(k, key_begin, max_blocks).bytes);
+      if (batch_has_tiled(n_segs, max_blocks, true)) *ws_bytes = bloom_oversize_ws_bytes(segs, n_segs);
+    }
   }
   if (max_blocks_out) *max_blocks_out = max_blocks;
   return TKV_AMQ_OK;
@@ -6217,149 +6518,29 @@ static int build_batch(int kind, const uint8_t* keys, const uint64_t* offs, uint
   const hipStream_t s = as_stream(stream);
   const int mode = key_mode(offs, stride);
   if (mode == kKey16 && (reinterpret_cast<uintptr_t>(keys) & 15)) return TKV_AMQ_INVALID_ARGUMENT;
+  const BuildArgs b{keys, offs, stride, n_keys, d_segs, n_segs, max_blocks, d_out, d_ws, ws_bytes, s, mode,
+                    build_key_mode(keys, offs, stride)};
 
   if (kind == TKV_AMQ_BLOOM) {
-    const uint64_t lds = 64ull * max_blocks;
     if (max_blocks == 0) return TKV_AMQ_OK;
-    const uint32_t parts = bloom_split_parts(n_segs, sizing_keys, max_blocks);
-    const uint64_t split_ws = bloom_split_ws_bytes(n_segs, parts, max_blocks);
-    if (parts > 1 && d_ws && ws_bytes >= split_ws) {
-      // a small batch: each leaf's keys over `parts` workgroups, then their images ORed
-      static std::once_flag split_attr[kMaxDevices];
-      once_per_device(split_attr, [] {
-        const int cap = (int)kBloomLeafLdsBudget;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bloom_build_split<kKey16>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bloom_build_split<kKey24>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bloom_build_split<kKeyFixed>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bloom_build_split<kKeyVar>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-      });
-      const int bmode = build_key_mode(keys, offs, stride);
-      const dim3 grid(n_segs * parts), block(kSplitThreads);
-      uint8_t* w = static_cast<uint8_t*>(d_ws);
-      const uint64_t img = 64ull * max_blocks;
-      if (bmode == kKey24)
-        hipLaunchKernelGGL(bloom_build_split<kKey24>, grid, block, lds, s, keys, offs, stride, d_segs,
-                           parts, w, img);
-      else if (mode == kKey16)
-        hipLaunchKernelGGL(bloom_build_split<kKey16>, grid, block, lds, s, keys, offs, stride, d_segs,
-                           parts, w, img);
-      else if (mode == kKeyFixed)
-        hipLaunchKernelGGL(bloom_build_split<kKeyFixed>, grid, block, lds, s, keys, offs, stride,
-                           d_segs, parts, w, img);
-      else
-        hipLaunchKernelGGL(bloom_build_split<kKeyVar>, grid, block, lds, s, keys, offs, stride, d_segs,
-                           parts, w, img);
-      const uint32_t chunks = (uint32_t)div_up(4ull * max_blocks, kMergeThreads);
-      hipLaunchKernelGGL(bloom_split_merge, dim3(n_segs * chunks), dim3(kMergeThreads), 0, s, d_segs,
-                         parts, chunks, w, img, d_out);
-      return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
-    }
-    // one filter beyond the window path: 16- and 24-byte keys take the monolithic build (each
-    // key hashed once); 24-byte keys with k > 8 only up to kDirectMaxTiles tiles (their records
-    // hold eight bits, and the others are set from the keys, which the route does not carry)
-    const int mono_mode = build_key_mode(keys, offs, stride);
-    const bool mono_part = bloom_partitioned(n_segs, max_blocks, sizing_keys) && d_ws;
-    const MonoPlan mp = mono_plan(sizing_keys, max_blocks);
-    const bool mono16 = mono_part && mode == kKey16 && ws_bytes >= mp.bytes;
-    // (routed 24-byte keys travel as bit records only: k must be known -- bloom_k_of 0 means
-    // the plan does not match n_keys -- and at most 8)
-    const uint32_t k_route = bloom_k_of(sizing_keys, max_blocks);
-    const bool mono24 = mono_part && mono_mode == kKey24 && ws_bytes >= mp.bytes &&
-                        (mp.g == 1 || (mp.blocks && k_route >= 1 && k_route <= 8));
-    if (bloom_window_path(n_segs, max_blocks, mono16 || mono24)) {
-      // leaves beyond one CU's LDS: windows of the image, parts of the keys
-      const uint32_t W = bloom_window_count(max_blocks), wblk = bloom_window_blocks(max_blocks);
-      uint32_t wparts = bloom_window_parts(n_segs, sizing_keys, max_blocks);
-      if (wparts > 1 && (!d_ws || ws_bytes < bloom_split_ws_bytes(n_segs, wparts, max_blocks)))
-        wparts = 1;  // no workspace for partial images: one part per leaf, no merge
-      static std::once_flag win_attr[kMaxDevices];
-      once_per_device(win_attr, [] {
-        for (const void* f : {reinterpret_cast<const void*>(&bloom_build_window<kKey16>),
-                              reinterpret_cast<const void*>(&bloom_build_window<kKey24>),
-                              reinterpret_cast<const void*>(&bloom_build_window<kKeyFixed>),
-                              reinterpret_cast<const void*>(&bloom_build_window<kKeyVar>)})
-          (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kBloomLeafLdsBudget);
-      });
-      const int bmode = build_key_mode(keys, offs, stride);
-      const dim3 grid(n_segs * W * wparts), block(kWinThreads);
-      const size_t wl = 64ull * wblk;
-      uint8_t* w = static_cast<uint8_t*>(d_ws);
-      const uint64_t img = 64ull * max_blocks;
-      if (bmode == kKey24)
-        hipLaunchKernelGGL(bloom_build_window<kKey24>, grid, block, wl, s, keys, offs, stride, d_segs,
-                           W, wblk, wparts, w, img, d_out);
-      else if (mode == kKey16)
-        hipLaunchKernelGGL(bloom_build_window<kKey16>, grid, block, wl, s, keys, offs, stride, d_segs,
-                           W, wblk, wparts, w, img, d_out);
-      else if (mode == kKeyFixed)
-        hipLaunchKernelGGL(bloom_build_window<kKeyFixed>, grid, block, wl, s, keys, offs, stride, d_segs,
-                           W, wblk, wparts, w, img, d_out);
-      else
-        hipLaunchKernelGGL(bloom_build_window<kKeyVar>, grid, block, wl, s, keys, offs, stride, d_segs,
-                           W, wblk, wparts, w, img, d_out);
-      if (wparts > 1) {
-        const uint32_t chunks = (uint32_t)div_up(4ull * max_blocks, kMergeThreads);
-        hipLaunchKernelGGL(bloom_split_merge, dim3(n_segs * chunks), dim3(kMergeThreads), 0, s, d_segs,
-                           wparts, chunks, w, img, d_out);
-      }
-      return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
-    }
-    if (lds <= kBloomLeafLdsBudget && n_segs >= kBloomSpreadSegs) {
-      const int bmode = build_key_mode(keys, offs, stride);
-      // (variable-length keys add their length-sort scratch: kVarAuxWords)
-      if (lds + (mode == kKeyVar ? 4ull * kVarAuxWords<1024> : 0ull) > kBloomLdsBudget) {
-        static std::once_flag big_attr[kMaxDevices];
-        once_per_device(big_attr, [] {
-          for (const void* f : {reinterpret_cast<const void*>(&bloom_build_lds<kKey16, 1024>),
-                                reinterpret_cast<const void*>(&bloom_build_lds<kKey24, 1024>),
-                                reinterpret_cast<const void*>(&bloom_build_lds<kKeyFixed, 1024>),
-                                reinterpret_cast<const void*>(&bloom_build_lds<kKeyVar, 1024>)})
-            (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kBloomLeafLdsBudget);
-        });
-      }
-      if (n_segs < kBloomWideSegs || lds > kBloomWideLds)
-        launch_bloom_lds<1024>(bmode, mode, n_segs, lds, s, keys, offs, stride, d_segs, d_out);
-      else
-        launch_bloom_lds<256>(bmode, mode, n_segs, lds, s, keys, offs, stride, d_segs, d_out);
-      return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
-    }
-    const bool mono_any = mono_part && !mono16 && !mono24 && mode != kKey16 && mono_mode != kKey24 &&
-                          any_tiled_ok(k_route, sizing_keys, max_blocks) &&
-                          ws_bytes >= any_plan(k_route, sizing_keys, max_blocks).bytes;
-    if (mono16 || mono24) {
-      // one monolithic filter: every key hashed once into its bit record, records partitioned
-      // by tile (routed into parts first beyond kDirectMaxTiles tiles), tiles built in LDS
-      launch_mono(mp, s, keys, mono24 ? 24u : 16u, (uint32_t)sizing_keys, d_segs, static_cast<uint8_t*>(d_ws),
-                  d_out);
-    } else if (mono_any) {
-      // one filter of variable-length or other fixed-size keys: the same, from bit records
-      // (bloom_any_records)
-      launch_any(any_plan(k_route, sizing_keys, max_blocks), k_route, s, keys, mode == kKeyVar ? offs : nullptr, stride,
-                 (uint32_t)sizing_keys, d_segs, static_cast<uint8_t*>(d_ws), d_out);
-    } else {
-      // fewer than kBloomSpreadSegs leaves, leaves beyond the LDS budget in a multi-leaf batch,
-      // or a monolithic filter whose keys are neither 16 nor 24 bytes (or 24-byte keys with
-      // k > 8 beyond kDirectMaxTiles tiles): device atomics
-      const dim3 g1(n_segs), b(256);
-      hipLaunchKernelGGL(bloom_global_init, g1, b, 0, s, d_segs, d_out);
-      const uint32_t g2 = (uint32_t)(div_up(n_keys, 256) < 8192 ? div_up(n_keys, 256) : 8192);
-      if (g2) {
-        if (mode == kKey16)
-          hipLaunchKernelGGL(bloom_global_set<kKey16>, dim3(g2), b, 0, s, keys, offs, stride,
-                             d_segs, n_segs, n_keys, d_out, 0ull);
-        else if (mode == kKeyFixed)
-          hipLaunchKernelGGL(bloom_global_set<kKeyFixed>, dim3(g2), b, 0, s, keys, offs, stride,
-                             d_segs, n_segs, n_keys, d_out, 0ull);
-        else
-          hipLaunchKernelGGL(bloom_global_set<kKeyVar>, dim3(g2), b, 0, s, keys, offs, stride,
-                             d_segs, n_segs, n_keys, d_out, 0ull);
-      }
+    const BloomPlan p = bloom_route(n_segs, sizing_keys, max_blocks, b.bmode, bloom_k_of(sizing_keys, max_blocks),
+                                    d_ws != nullptr, ws_bytes);
+    uint8_t* ws = static_cast<uint8_t*>(d_ws);
+    switch (p.route) {
+      case BloomRoute::Split: launch_bloom_split(b, p); break;
+      case BloomRoute::Window: launch_bloom_window(b, p); break;
+      case BloomRoute::Lds:
+        if (p.threads == 1024) launch_bloom_lds<1024>(b.bmode, n_segs, 64ull * max_blocks, s, keys, offs, stride, d_segs, d_out);
+        else launch_bloom_lds<256>(b.bmode, n_segs, 64ull * max_blocks, s, keys, offs, stride, d_segs, d_out);
+        break;
+      case BloomRoute::TiledKeys:
+        launch_mono(p.mono, s, keys, b.bmode == kKey24 ? 24u : 16u, (uint32_t)sizing_keys, d_segs, ws, d_out);
+        break;
+      case BloomRoute::TiledRecords:
+        launch_any(p.any, bloom_k_of(sizing_keys, max_blocks), s, keys, mode == kKeyVar ? offs : nullptr, stride,
+                   (uint32_t)sizing_keys, d_segs, ws, d_out);
+        break;
+      case BloomRoute::Atomics: launch_bloom_atomics(s, mode, keys, offs, stride, d_segs, n_segs, 0, n_keys, d_out); break;
     }
     return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
   }
@@ -6379,191 +6560,46 @@ static int build_batch(int kind, const uint8_t* keys, const uint64_t* offs, uint
     return TKV_AMQ_INVALID_ARGUMENT;
   // (no memset: every decide workgroup writes the header's leaf count and its leaf's nelts
   // word, flags included, so tkv_amq_build_check reads only this build's results)
-  // LDS: u32 block counts (+ the u64 lane-mask table when every leaf is small enough)
-  // The lane-mask table costs 8 B of LDS per block in every decide wave, and wins even where
-  // it costs waves per CU: 6,104 leaves of 804 blocks 2.49 -> 2.14 ms (16 instead of 24 waves
-  // per CU), 2,048 of 1,961 blocks 3.03 -> 2.52 ms, against block-id ballots
-  const int match_lds = max_blocks <= kVqfMatchLdsBlocks;
-  // a leaf whose LDS image exceeds the budget is placed by up to kFusedMaxParts workgroups
-  const uint32_t place_parts =
-      (uint32_t)div_up(max_blocks, kFusedLdsBudget / (4 * kFusedRegionWords));
-  const uint32_t place_span = (uint32_t)div_up(max_blocks, place_parts);
-  const uint32_t fused_lds = vqf_fused_lds_bytes(place_span);
-  const bool fused = place_parts <= kFusedMaxParts;  // compact records are read only there
-  // the count table: u32 in LDS up to kVqfMaxLdsBlocks, u8 in LDS up to kVqfU8LdsBlocks, else
-  // in the workspace's block records (VqfCountMode)
-  const int cnt_mode = max_blocks <= kVqfMaxLdsBlocks ? kCntU32
-                       : (max_blocks <= kVqfU8LdsBlocks ? kCntU8 : kCntGlobal);
-  const int flags = match_lds | (fused ? 2 : 0);
-  const size_t lds = cnt_mode == kCntU8 ? (size_t)((max_blocks + 15) & ~15u)
-                     : cnt_mode == kCntGlobal ? 16
-                     : 4ull * ((max_blocks + 1) & ~1u) + (match_lds ? 8ull * max_blocks : 0);
-  const int vmode = build_key_mode(keys, offs, stride);
-  if (cnt_mode != kCntU32) {
-    // a leaf past the u32 count table: vqf_decide_big for the whole batch (fused place is out
-    // of reach for such a leaf, so the records are the 8-byte ones)
-    static std::once_flag big_attr[kMaxDevices];
-    once_per_device(big_attr, [] {
-      for (const void* f : {reinterpret_cast<const void*>(&vqf_decide_big<kKey16, kCntU8>),
-                            reinterpret_cast<const void*>(&vqf_decide_big<kKey24, kCntU8>),
-                            reinterpret_cast<const void*>(&vqf_decide_big<kKeyFixed, kCntU8>),
-                            reinterpret_cast<const void*>(&vqf_decide_big<kKeyVar, kCntU8>)})
-        (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    const dim3 g(n_segs), b(64);
-#define TKV_DECIDE_BIG(CNT)                                                                         \
-  do {                                                                                              \
-    if (vmode == kKey16)                                                                            \
-      hipLaunchKernelGGL((vqf_decide_big<kKey16, CNT>), g, b, lds, s, keys, offs, stride, d_segs, d_ws, \
-                         ws_bytes, n_segs);                                                         \
-    else if (vmode == kKey24)                                                                       \
-      hipLaunchKernelGGL((vqf_decide_big<kKey24, CNT>), g, b, lds, s, keys, offs, stride, d_segs, d_ws, \
-                         ws_bytes, n_segs);                                                         \
-    else if (mode == kKeyFixed)                                                                     \
-      hipLaunchKernelGGL((vqf_decide_big<kKeyFixed, CNT>), g, b, lds, s, keys, offs, stride, d_segs,    \
-                         d_ws, ws_bytes, n_segs);                                                   \
-    else                                                                                            \
-      hipLaunchKernelGGL((vqf_decide_big<kKeyVar, CNT>), g, b, lds, s, keys, offs, stride, d_segs,      \
-                         d_ws, ws_bytes, n_segs);                                                   \
-  } while (0)
-    if (cnt_mode == kCntU8) TKV_DECIDE_BIG(kCntU8);
-    else TKV_DECIDE_BIG(kCntGlobal);
-#undef TKV_DECIDE_BIG
-  }
-  // the ring kernel for small batches of leaves its count table holds (a batch with a larger
-  // leaf takes vqf_decide: the one-wave body inside the ring kernel set its registers, and so
-  // its workgroups per CU, for every batch).  Keys other than 16 bytes are read where they are
-  // hashed, which puts their load latency on vqf_decide's serial chain: the ring kernel, whose
-  // producers hash off the chain, stays faster up to ~4,096 leaves for them (1,024 leaves of
-  // 24-byte keys 0.47 -> 0.29 ms, variable-length 0.66 -> 0.38 ms; at 6,104 leaves vqf_decide
-  // wins, 1.25 vs 1.45 ms)
-  // 24-byte keys (TurtleKV's default key size hint), 8-byte aligned, are loaded ahead of
-  // their hash like 16-byte ones
-  const bool prefetched = vmode == kKey16 || vmode == kKey24;
-  const bool rp1 = n_segs <= kRingPlaceMaxSegs && max_blocks <= kRingPlaceMaxBlocks;
-  const bool rp2 = !rp1 && n_segs <= kRingPlace2MaxSegs && max_blocks <= kRingPlace2MaxBlocks;
-  if (cnt_mode == kCntU32 && (rp1 || rp2)) {
-    // decide and place in one workgroup per leaf (vqf_ring_place): no key records, one launch;
-    // up to 256 leaves one workgroup per CU (ring of kRingPlaceSlots, match tables), up to 512 two
-    static std::once_flag rp_attr[kMaxDevices];
-    once_per_device(rp_attr, [] {
-      for (const void* f : {reinterpret_cast<const void*>(&vqf_ring_place<kKey16, kRingPlaceSlots>),
-                            reinterpret_cast<const void*>(&vqf_ring_place<kKey24, kRingPlaceSlots>),
-                            reinterpret_cast<const void*>(&vqf_ring_place<kKeyFixed, kRingPlaceSlots>),
-                            reinterpret_cast<const void*>(&vqf_ring_place<kKeyVar, kRingPlaceSlots>),
-                            reinterpret_cast<const void*>(&vqf_ring_place<kKey16, kRingPlace2Slots>),
-                            reinterpret_cast<const void*>(&vqf_ring_place<kKey24, kRingPlace2Slots>),
-                            reinterpret_cast<const void*>(&vqf_ring_place<kKeyFixed, kRingPlace2Slots>),
-                            reinterpret_cast<const void*>(&vqf_ring_place<kKeyVar, kRingPlace2Slots>),
-                            reinterpret_cast<const void*>(&vqf_ring_place<kKeyLoc, kRingPlaceSlots>),
-                            reinterpret_cast<const void*>(&vqf_ring_place<kKeyLoc, kRingPlace2Slots>)})
-        (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    const dim3 g(n_segs), b(kRingThreads);
-    const uint32_t cw = ring_place_cnt_words(max_blocks);
-    const uint32_t tbl = rp1 && max_blocks <= kRingTblBlocks;  // (ring_place_lds_bytes sizes them)
-    const size_t rl = rp1 ? ring_place_lds_bytes(max_blocks) : ring_place_lds_bytes(max_blocks, kRingPlace2Slots, false);
-    // keys read where they are hashed (other than 16 or 24 bytes: the producers, not the
-    // decider, set a lone leaf's time): every key hashed and located on the whole chip first
-    // (vqf_locate_keys), the ring's producers then read 8-byte located records
-    const bool loc = !prefetched && n_segs <= (mode == kKeyVar ? kVqfLocMaxSegsVar : kVqfLocMaxSegsFixed);
-    if (loc && n_keys > 0) {
-      const dim3 lg((uint32_t)div_up(n_keys, 256)), lb(256);
-      if (mode == kKeyFixed)
-        hipLaunchKernelGGL(vqf_locate_keys<kKeyFixed>, lg, lb, 0, s, keys, offs, stride, d_segs, d_ws, ws_bytes, n_segs,
-                           n_keys);
-      else
-        hipLaunchKernelGGL(vqf_locate_keys<kKeyVar>, lg, lb, 0, s, keys, offs, stride, d_segs, d_ws, ws_bytes, n_segs,
-                           n_keys);
+  const VqfPlan p = vqf_route(n_segs, max_blocks, b.bmode, n_keys);
+  const dim3 dg(n_segs), wave(64);
+  with_build_key_mode(b.bmode, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    switch (p.decide) {
+      case VqfDecide::BigU8:
+        launch_lds_cap<&vqf_decide_big<MODE, kCntU8>>(kVqfLdsCap, dg, wave, p.lds, s, keys, offs, stride, d_segs, d_ws,
+                                                      ws_bytes, n_segs);
+        break;
+      case VqfDecide::BigGlobal:
+        hipLaunchKernelGGL((vqf_decide_big<MODE, kCntGlobal>), dg, wave, p.lds, s, keys, offs, stride, d_segs, d_ws,
+                           ws_bytes, n_segs);
+        break;
+      case VqfDecide::RingPlace: launch_ring_place<MODE, kRingPlaceSlots>(b, p); break;
+      case VqfDecide::RingPlace2: launch_ring_place<MODE, kRingPlace2Slots>(b, p); break;
+      case VqfDecide::Ring:
+        launch_lds_cap<&vqf_decide_ring<MODE>>(kVqfLdsCap, dg, dim3(kRingThreads), p.rl, s, keys, offs, stride, d_segs, d_ws,
+                                               ws_bytes, n_segs, p.flags);
+        break;
+      case VqfDecide::Decide:
+        hipLaunchKernelGGL(vqf_decide<MODE>, dg, wave, p.lds, s, keys, offs, stride, d_segs, d_ws, ws_bytes, n_segs, p.flags);
+        break;
     }
-#define TKV_RING_PLACE(NS)                                                                              \
-  do {                                                                                                  \
-    if (loc)                                                                                            \
-      hipLaunchKernelGGL((vqf_ring_place<kKeyLoc, NS>), g, b, rl, s, nullptr, nullptr, 0, d_segs, d_ws,   \
-                         ws_bytes, n_segs, d_out, cw, tbl);                                             \
-    else if (vmode == kKey16)                                                                           \
-      hipLaunchKernelGGL((vqf_ring_place<kKey16, NS>), g, b, rl, s, keys, offs, stride, d_segs, d_ws,     \
-                         ws_bytes, n_segs, d_out, cw, tbl);                                             \
-    else if (vmode == kKey24)                                                                           \
-      hipLaunchKernelGGL((vqf_ring_place<kKey24, NS>), g, b, rl, s, keys, offs, stride, d_segs, d_ws,     \
-                         ws_bytes, n_segs, d_out, cw, tbl);                                             \
-    else if (mode == kKeyFixed)                                                                         \
-      hipLaunchKernelGGL((vqf_ring_place<kKeyFixed, NS>), g, b, rl, s, keys, offs, stride, d_segs, d_ws,  \
-                         ws_bytes, n_segs, d_out, cw, tbl);                                             \
-    else                                                                                                \
-      hipLaunchKernelGGL((vqf_ring_place<kKeyVar, NS>), g, b, rl, s, keys, offs, stride, d_segs, d_ws,    \
-                         ws_bytes, n_segs, d_out, cw, tbl);                                             \
-  } while (0)
-    if (rp1) TKV_RING_PLACE(kRingPlaceSlots);
-    else TKV_RING_PLACE(kRingPlace2Slots);
-#undef TKV_RING_PLACE
-    return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
-  }
-  if (cnt_mode != kCntU32) {
-    // (decided above)
-  } else if (n_segs <= (prefetched ? kVqfRingMaxSegs : kVqfRingMaxSegsOther) &&
-             max_blocks <= kRingMaxBlocks) {
-    static std::once_flag ring_attr[kMaxDevices];
-    once_per_device(ring_attr, [] {
-      for (const void* f : {reinterpret_cast<const void*>(&vqf_decide_ring<kKey16>),
-                            reinterpret_cast<const void*>(&vqf_decide_ring<kKey24>),
-                            reinterpret_cast<const void*>(&vqf_decide_ring<kKeyFixed>),
-                            reinterpret_cast<const void*>(&vqf_decide_ring<kKeyVar>)})
-        (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    const dim3 g(n_segs), b(kRingThreads);
-    const size_t rl = lds > kRingLdsBytes ? lds : kRingLdsBytes;
-    if (vmode == kKey16)
-      hipLaunchKernelGGL(vqf_decide_ring<kKey16>, g, b, rl, s, keys, offs, stride, d_segs, d_ws,
-                         ws_bytes, n_segs, flags);
-    else if (vmode == kKey24)
-      hipLaunchKernelGGL(vqf_decide_ring<kKey24>, g, b, rl, s, keys, offs, stride, d_segs, d_ws,
-                         ws_bytes, n_segs, flags);
-    else if (mode == kKeyFixed)
-      hipLaunchKernelGGL(vqf_decide_ring<kKeyFixed>, g, b, rl, s, keys, offs, stride, d_segs, d_ws,
-                         ws_bytes, n_segs, flags);
-    else
-      hipLaunchKernelGGL(vqf_decide_ring<kKeyVar>, g, b, rl, s, keys, offs, stride, d_segs, d_ws,
-                         ws_bytes, n_segs, flags);
-  } else if (vmode == kKey16)
-    hipLaunchKernelGGL(vqf_decide<kKey16>, dim3(n_segs), dim3(64), lds, s, keys, offs, stride,
-                       d_segs, d_ws, ws_bytes, n_segs, flags);
-  else if (vmode == kKey24)
-    hipLaunchKernelGGL(vqf_decide<kKey24>, dim3(n_segs), dim3(64), lds, s, keys, offs, stride,
-                       d_segs, d_ws, ws_bytes, n_segs, flags);
-  else if (mode == kKeyFixed)
-    hipLaunchKernelGGL(vqf_decide<kKeyFixed>, dim3(n_segs), dim3(64), lds, s, keys, offs, stride,
-                       d_segs, d_ws, ws_bytes, n_segs, flags);
-  else
-    hipLaunchKernelGGL(vqf_decide<kKeyVar>, dim3(n_segs), dim3(64), lds, s, keys, offs, stride,
-                       d_segs, d_ws, ws_bytes, n_segs, flags);
-  if (fused) {
-    static std::once_flag lds_attr[kMaxDevices];
-    once_per_device(lds_attr, [] {
-      for (const void* f : {reinterpret_cast<const void*>(&vqf_place_fused<256>),
-                            reinterpret_cast<const void*>(&vqf_place_fused<512>)})
-        (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLdsBudget);
-    });
-    // 512 threads for a batch that does not fill the chip (the ring-decide sizes) or leaves of
-    // more than 512 blocks: lone leaf 98 -> 95 us, 2,048 x 80K keys 2.51 -> 2.30 ms; 256 for a
-    // full batch of small leaves (0.709 vs 0.697 ms at 100M keys)
-    const dim3 pg(n_segs * place_parts);
-    if (n_segs <= kVqfRingMaxSegs || max_blocks > 512)
-      hipLaunchKernelGGL(vqf_place_fused<512>, pg, dim3(512), fused_lds, s, d_segs, d_ws, ws_bytes,
-                         n_segs, d_out, place_parts, place_span);
-    else
-      hipLaunchKernelGGL(vqf_place_fused<256>, pg, dim3(256), fused_lds, s, d_segs, d_ws, ws_bytes,
-                         n_segs, d_out, place_parts, place_span);
-  } else {
-    if (n_keys)
-      hipLaunchKernelGGL(vqf_scatter, dim3((uint32_t)div_up(n_keys, 256)), dim3(256), 0, s,
-                         d_segs, d_ws, ws_bytes, n_segs, n_keys);
-    // several workgroups per leaf for large leaves (each takes every parts-th group of
-    // kPlaceThreads blocks)
-    const uint32_t parts = (uint32_t)(div_up(max_blocks, 4 * kPlaceThreads) < 256
-                                          ? div_up(max_blocks, 4 * kPlaceThreads) : 256);
-    hipLaunchKernelGGL(vqf_place, dim3(n_segs * parts), dim3(kPlaceThreads), 0, s, d_segs, d_ws,
-                       ws_bytes, n_segs, d_out, parts);
+  });
+  const dim3 pg(n_segs * p.place_parts);
+  switch (p.place) {
+    case VqfPlace::None: break;
+    case VqfPlace::Fused512:
+      launch_lds_cap<&vqf_place_fused<512>>(kFusedLdsBudget, pg, dim3(512), vqf_fused_lds_bytes(p.place_span), s, d_segs,
+                                            d_ws, ws_bytes, n_segs, d_out, p.place_parts, p.place_span);
+      break;
+    case VqfPlace::Fused256:
+      launch_lds_cap<&vqf_place_fused<256>>(kFusedLdsBudget, pg, dim3(256), vqf_fused_lds_bytes(p.place_span), s, d_segs,
+                                            d_ws, ws_bytes, n_segs, d_out, p.place_parts, p.place_span);
+      break;
+    case VqfPlace::Scatter:
+      if (p.key_wgs)
+        hipLaunchKernelGGL(vqf_scatter, dim3(p.key_wgs), dim3(256), 0, s, d_segs, d_ws, ws_bytes, n_segs, n_keys);
+      hipLaunchKernelGGL(vqf_place, pg, dim3(kPlaceThreads), 0, s, d_segs, d_ws, ws_bytes, n_segs, d_out, p.place_parts);
+      break;
   }
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
@@ -6574,7 +6610,7 @@ int tkv_amq_build_ex(int kind, const uint8_t* keys, const uint64_t* offs, uint32
 {
   const int mode = key_mode(offs, stride), bmode = build_key_mode(keys, offs, stride);
   const bool fixed = mode == kKey16 || bmode == kKey24;  // the tiled build takes these keys
-  if (kind != TKV_AMQ_BLOOM || !h_segs || n_segs < 2 || !batch_tiled(max_blocks, fixed))
+  if (kind != TKV_AMQ_BLOOM || !h_segs || !batch_has_tiled(n_segs, max_blocks, fixed))
     return tkv_amq_build(kind, keys, offs, stride, n_keys, d_segs, n_segs, max_blocks, d_out, d_ws, ws_bytes,
                          stream);
   if (tkv_amq_device_count() == 0) return TKV_AMQ_UNAVAILABLE;
@@ -6624,7 +6660,6 @@ int tkv_amq_build_ex(int kind, const uint8_t* keys, const uint64_t* offs, uint32
     wgs = tiles = 0;
     lds = 0;
   };
-  const bool multi_keys = fixed;
   uint32_t n_multi = 0;
   const uint64_t tiled_keys = multi_keys_of(h_segs, n_segs, &n_multi);
   const uint64_t wg_items = multi_wg_items(tiled_keys);
@@ -6632,11 +6667,11 @@ int tkv_amq_build_ex(int kind, const uint8_t* keys, const uint64_t* offs, uint32
   const uint32_t per_launch = n_multi ? (uint32_t)div_up(n_multi, div_up(n_multi, kMultiMaxLeaves)) : 1u;
   for (uint32_t i = 0; i < n_segs; ++i) {
     const tkv_amq_segment& g = h_segs[i];
-    if (!batch_tiled(g.n_blocks, fixed) || g.bits_per_key == 0) continue;
-    if (multi_keys && multi_leaf(g.n_keys, g.n_blocks)) {
-      const PartGeom pg = multi_geom(g.n_keys, g.n_blocks, wg_items);
-      const uint64_t b = align256(pg.bytes);
-      if (b <= mbudget) {
+    const LeafRoute r = bloom_leaf(g, fixed, bmode, wg_items, rest_bytes);
+    switch (r.kind) {
+      case TKV_AMQ_LEAF_MULTI: {
+        const PartGeom& pg = r.pg;
+        const uint64_t b = align256(pg.bytes);
         if (m.n == per_launch || used + b > mbudget) flush();
         MultiLeaf& l = m.l[m.n];
         l = MultiLeaf{};
@@ -6659,42 +6694,85 @@ int tkv_amq_build_ex(int kind, const uint8_t* keys, const uint64_t* offs, uint32
         wgs += pg.P;
         tiles += pg.n_tiles;
         lds = std::max(lds, multi_lds_bytes(pg.n_tiles));
-        continue;
+        break;
       }
-    }
-    const MonoPlan mp = mono_plan(g.n_keys, g.n_blocks);
-    const uint32_t k = bloom_k_of(g.n_keys, g.n_blocks);
-    const bool mono = rest_bytes >= mp.bytes &&
-                      (mode == kKey16 || (bmode == kKey24 && (mp.g == 1 || (mp.blocks && k >= 1 && k <= 8))));
-    const bool any = !mono && mode != kKey16 && bmode != kKey24 && any_tiled_ok(g.hash_count, g.n_keys, g.n_blocks) &&
-                     rest_bytes >= any_plan(g.hash_count, g.n_keys, g.n_blocks).bytes;
-    if (mono) {
-      launch_mono(mp, s, keys, mode == kKey16 ? 16u : 24u, g.n_keys, d_segs + i, rest, d_out, g.key_begin);
-    } else if (any) {
-      // variable-length or other fixed-size keys: hashed into bit records (bloom_any_records),
-      // then the tiled build
-      launch_any(any_plan(g.hash_count, g.n_keys, g.n_blocks), g.hash_count, s, keys, mode == kKeyVar ? offs : nullptr, stride,
-                 (uint32_t)g.n_keys, d_segs + i, rest, d_out);
-    } else {
-      // other key shapes past k = 16 (or no room): device atomics for this leaf alone
-      hipLaunchKernelGGL(bloom_global_init, dim3(1), dim3(256), 0, s, d_segs + i, d_out);
-      const uint32_t g2 = (uint32_t)std::min<uint64_t>(div_up(g.n_keys, 256), 8192);
-      if (g2) {
-        const uint64_t end = g.key_begin + g.n_keys;
-        if (mode == kKey16)
-          hipLaunchKernelGGL(bloom_global_set<kKey16>, dim3(g2), dim3(256), 0, s, keys, offs, stride, d_segs + i, 1u,
-                             end, d_out, g.key_begin);
-        else if (mode == kKeyFixed)
-          hipLaunchKernelGGL(bloom_global_set<kKeyFixed>, dim3(g2), dim3(256), 0, s, keys, offs, stride, d_segs + i,
-                             1u, end, d_out, g.key_begin);
-        else
-          hipLaunchKernelGGL(bloom_global_set<kKeyVar>, dim3(g2), dim3(256), 0, s, keys, offs, stride, d_segs + i,
-                             1u, end, d_out, g.key_begin);
-      }
+      case TKV_AMQ_LEAF_TILED_KEYS:
+        launch_mono(r.plan.mono, s, keys, mkb, g.n_keys, d_segs + i, rest, d_out, g.key_begin);
+        break;
+      case TKV_AMQ_LEAF_TILED_RECORDS:
+        launch_any(r.plan.any, g.hash_count, s, keys, mode == kKeyVar ? offs : nullptr, stride, (uint32_t)g.n_keys,
+                   d_segs + i, rest, d_out);
+        break;
+      case TKV_AMQ_LEAF_ATOMICS:
+        // other key shapes past k = 16 (or no room): device atomics for this leaf alone
+        launch_bloom_atomics(s, mode, keys, offs, stride, d_segs + i, 1u, g.key_begin, g.key_begin + g.n_keys, d_out);
+        break;
+      default: break;  // (in the compacted batch, or no filter)
     }
   }
   flush();
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
+}
+
+static void report_route(const BloomPlan& p, struct tkv_amq_build_route* out)
+{
+  out->route = (uint32_t)p.route;
+  out->place = TKV_AMQ_PLACE_NONE;
+  out->parts = p.parts;
+  out->windows = p.windows;
+  out->threads = p.threads;
+  out->ws_bytes = p.ws_bytes;
+  out->lds_bytes = p.lds_bytes;
+}
+
+int tkv_amq_build_route(int kind, uint32_t stride, int has_offsets, int keys_aligned8, uint32_t n_segs,
+                        uint64_t n_keys, uint32_t max_blocks, const tkv_amq_segment* h_segs, int have_ws,
+                        uint64_t ws_bytes, struct tkv_amq_build_route* out, uint8_t* leaf_route)
+{
+  if (!out || (!has_offsets && stride == 0) || (kind != TKV_AMQ_BLOOM && kind != TKV_AMQ_VQF))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  memset(out, 0, sizeof(*out));
+  for (uint32_t i = 0; leaf_route && i < n_segs; ++i) leaf_route[i] = TKV_AMQ_LEAF_BATCH;
+  if (n_segs == 0 || max_blocks == 0) return TKV_AMQ_OK;
+  const int mode = key_mode_of(has_offsets != 0, stride);
+  const int bmode = build_key_mode_of(has_offsets != 0, stride, keys_aligned8 != 0);
+  if (kind == TKV_AMQ_VQF) {
+    if (max_blocks > kVqfMaxBlocks) return TKV_AMQ_RESOURCE_EXHAUSTED;
+    const VqfPlan p = vqf_route(n_segs, max_blocks, bmode, n_keys);
+    out->route = (uint32_t)p.decide;
+    out->place = (uint32_t)p.place;
+    out->parts = p.place_parts;
+    out->threads = p.decide == VqfDecide::RingPlace || p.decide == VqfDecide::RingPlace2 || p.decide == VqfDecide::Ring
+                       ? kRingThreads : 64u;
+    out->located = p.located;
+    out->lds_bytes = (uint32_t)(p.rl ? p.rl : p.lds);
+    out->ws_bytes = vqf_temp_offset(n_segs) + kVqfTempStride * (uint64_t)max_blocks + 8 * n_keys;
+    return TKV_AMQ_OK;
+  }
+  const bool fixed = mode == kKey16 || bmode == kKey24;
+  if (!h_segs || !batch_has_tiled(n_segs, max_blocks, fixed)) {
+    report_route(bloom_route(n_segs, n_keys, max_blocks, bmode, bloom_k_of(n_keys, max_blocks), have_ws != 0, ws_bytes),
+                 out);
+    return TKV_AMQ_OK;
+  }
+  const uint64_t list_bytes = align256(64ull * n_segs);
+  if (!have_ws || ws_bytes < list_bytes) return TKV_AMQ_INVALID_ARGUMENT;
+  const uint64_t rest_bytes = ws_bytes - list_bytes;
+  const uint64_t wg_items = multi_wg_items(multi_keys_of(h_segs, n_segs));
+  uint32_t n_small = 0, small_max = 0;
+  uint64_t small_keys = 0;
+  for (uint32_t i = 0; i < n_segs; ++i) {
+    const uint32_t leaf = bloom_leaf(h_segs[i], fixed, bmode, wg_items, rest_bytes).kind;
+    if (leaf_route) leaf_route[i] = (uint8_t)leaf;
+    if (leaf != TKV_AMQ_LEAF_BATCH) continue;
+    ++n_small;
+    small_max = std::max(small_max, h_segs[i].n_blocks);
+    small_keys += h_segs[i].n_keys;
+  }
+  if (n_small && small_max)
+    report_route(bloom_route(n_small, small_keys, small_max, bmode, bloom_k_of(small_keys, small_max), true, rest_bytes),
+                 out);
+  return TKV_AMQ_OK;
 }
 
 uint32_t tkv_amq_bloom_tile_blocks(void) { return kTileBlocks; }
@@ -6982,25 +7060,18 @@ int tkv_amq_probe_ex(int kind, const uint8_t* d_filters, const tkv_amq_segment* 
   const tkv_amq_probe_opts o = probe_opts(opts);
   const bool ex = probe_opts_used(o);
   const dim3 grid(probe_grid(n, ex)), block(256);
-#define TKV_PROBE_LAUNCH(KERNEL, MODE)                                                         \
-  do {                                                                                         \
-    if (ex)                                                                                    \
-      hipLaunchKernelGGL((KERNEL<MODE, true>), grid, block, 0, s, d_filters, d_segs, n_segs, q, \
-                         qoffs, stride, n, d_qseg, d_result, o);                               \
-    else                                                                                       \
-      hipLaunchKernelGGL((KERNEL<MODE, false>), grid, block, 0, s, d_filters, d_segs, n_segs,  \
-                         q, qoffs, stride, n, d_qseg, d_result, o);                            \
-  } while (0)
-  if (kind == TKV_AMQ_BLOOM) {
-    if (mode == kKey16) TKV_PROBE_LAUNCH(bloom_probe, kKey16);
-    else if (mode == kKeyFixed) TKV_PROBE_LAUNCH(bloom_probe, kKeyFixed);
-    else TKV_PROBE_LAUNCH(bloom_probe, kKeyVar);
-  } else {
-    if (mode == kKey16) TKV_PROBE_LAUNCH(vqf_probe, kKey16);
-    else if (mode == kKeyFixed) TKV_PROBE_LAUNCH(vqf_probe, kKeyFixed);
-    else TKV_PROBE_LAUNCH(vqf_probe, kKeyVar);
-  }
-#undef TKV_PROBE_LAUNCH
+  with_key_mode(mode, [&](auto M) {
+    with_flag(ex, [&](auto X) {
+      constexpr int MODE = decltype(M)::value;
+      constexpr bool kOpts = decltype(X)::value;
+      if (kind == TKV_AMQ_BLOOM)
+        hipLaunchKernelGGL((bloom_probe<MODE, kOpts>), grid, block, 0, s, d_filters, d_segs, n_segs, q, qoffs, stride, n,
+                           d_qseg, d_result, o);
+      else
+        hipLaunchKernelGGL((vqf_probe<MODE, kOpts>), grid, block, 0, s, d_filters, d_segs, n_segs, q, qoffs, stride, n,
+                           d_qseg, d_result, o);
+    });
+  });
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
 
@@ -7014,12 +7085,9 @@ int tkv_amq_vqf_hash(const uint8_t* q, const uint64_t* qoffs, uint32_t stride, u
   const int mode = key_mode(qoffs, stride);
   if (mode == kKey16 && (reinterpret_cast<uintptr_t>(q) & 15)) return TKV_AMQ_INVALID_ARGUMENT;
   const dim3 grid((uint32_t)div_up(n, 256)), block(256);
-  if (mode == kKey16)
-    hipLaunchKernelGGL(vqf_hash_kernel<kKey16>, grid, block, 0, s, q, qoffs, stride, n, d_hash);
-  else if (mode == kKeyFixed)
-    hipLaunchKernelGGL(vqf_hash_kernel<kKeyFixed>, grid, block, 0, s, q, qoffs, stride, n, d_hash);
-  else
-    hipLaunchKernelGGL(vqf_hash_kernel<kKeyVar>, grid, block, 0, s, q, qoffs, stride, n, d_hash);
+  with_key_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL(vqf_hash_kernel<decltype(M)::value>, grid, block, 0, s, q, qoffs, stride, n, d_hash);
+  });
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
 
@@ -7066,12 +7134,9 @@ int tkv_amq_bloom_hash(const uint8_t* q, const uint64_t* qoffs, uint32_t stride,
   const int mode = key_mode(qoffs, stride);
   if (mode == kKey16 && (reinterpret_cast<uintptr_t>(q) & 15)) return TKV_AMQ_INVALID_ARGUMENT;
   const dim3 grid((uint32_t)div_up(n, 256)), block(256);
-  if (mode == kKey16)
-    hipLaunchKernelGGL(bloom_hash_kernel<kKey16>, grid, block, 0, s, q, qoffs, stride, n, k_max, d_query);
-  else if (mode == kKeyFixed)
-    hipLaunchKernelGGL(bloom_hash_kernel<kKeyFixed>, grid, block, 0, s, q, qoffs, stride, n, k_max, d_query);
-  else
-    hipLaunchKernelGGL(bloom_hash_kernel<kKeyVar>, grid, block, 0, s, q, qoffs, stride, n, k_max, d_query);
+  with_key_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL(bloom_hash_kernel<decltype(M)::value>, grid, block, 0, s, q, qoffs, stride, n, k_max, d_query);
+  });
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
 
@@ -7182,21 +7247,16 @@ int tkv_amq_path_probe(int kind, const uint8_t* d_filters, const tkv_amq_segment
   // with options: a bounded grid, so the metrics take one atomic per counter per wave (as
   // probe_grid does for the pair probes)
   const dim3 grid(ex && a.n_wgs > 8192u ? 8192u : a.n_wgs), block(256);
-#define TKV_PATH_LAUNCH(KIND, MODE)                                                              \
-  do {                                                                                           \
-    if (ex) hipLaunchKernelGGL((path_probe_kernel<KIND, MODE, true>), grid, block, 0, s, a, o);  \
-    else hipLaunchKernelGGL((path_probe_kernel<KIND, MODE, false>), grid, block, 0, s, a, o);    \
-  } while (0)
-  if (kind == TKV_AMQ_BLOOM) {
-    if (mode == kKey16) TKV_PATH_LAUNCH(TKV_AMQ_BLOOM, kKey16);
-    else if (mode == kKeyFixed) TKV_PATH_LAUNCH(TKV_AMQ_BLOOM, kKeyFixed);
-    else TKV_PATH_LAUNCH(TKV_AMQ_BLOOM, kKeyVar);
-  } else {
-    if (mode == kKey16) TKV_PATH_LAUNCH(TKV_AMQ_VQF, kKey16);
-    else if (mode == kKeyFixed) TKV_PATH_LAUNCH(TKV_AMQ_VQF, kKeyFixed);
-    else TKV_PATH_LAUNCH(TKV_AMQ_VQF, kKeyVar);
-  }
-#undef TKV_PATH_LAUNCH
+  with_key_mode(mode, [&](auto M) {
+    with_flag(ex, [&](auto X) {
+      constexpr int MODE = decltype(M)::value;
+      constexpr bool kOpts = decltype(X)::value;
+      if (kind == TKV_AMQ_BLOOM)
+        hipLaunchKernelGGL((path_probe_kernel<TKV_AMQ_BLOOM, MODE, kOpts>), grid, block, 0, s, a, o);
+      else
+        hipLaunchKernelGGL((path_probe_kernel<TKV_AMQ_VQF, MODE, kOpts>), grid, block, 0, s, a, o);
+    });
+  });
   hipLaunchKernelGGL(path_scan_totals, dim3(1), dim3(256), 0, s, a.wg_total, a.n_wgs, d_cand_begin,
                      a.n_queries, a.n_entries);
   hipLaunchKernelGGL(path_scatter, dim3(a.n_wgs), block, 0, s, a);

@@ -564,6 +564,23 @@ def build_all_filters(plan: FilterPlan, keys: KeyBatch, out=None, workspace=None
     return out
 
 
+def build_route(plan: FilterPlan, key_stride: int = 16, has_offsets: bool = False,
+                aligned8: bool = True, workspace_bytes: int | None = None, ex: bool = True):
+    """The route build_all_filters (ex: tkv_amq_build_ex with the host plan; else tkv_amq_build)
+    takes for `plan` and such keys, without a device: (abi.BuildRoute, per-leaf abi.LEAF_*).
+    workspace_bytes None: the plan's workspace (none when the plan needs none)."""
+    ws = plan.workspace_bytes if workspace_bytes is None else int(workspace_bytes)
+    out = abi.BuildRoute()
+    leaves = np.zeros(plan.n_segs, dtype=np.uint8)
+    st = abi.lib().tkv_amq_build_route(plan.kind, 0 if has_offsets else int(key_stride),
+                                       int(bool(has_offsets)), int(bool(aligned8)), plan.n_segs,
+                                       plan.n_keys, plan.max_seg_blocks,
+                                       _ptr(plan.segs) if ex else None, int(ws > 0), ws,
+                                       ctypes.byref(out), _ptr(leaves))
+    abi.check(st, "tkv_amq_build_route")
+    return out, leaves
+
+
 class ProbeMetrics:
     """Device-side KeyQuery::Metrics counters (tkv_amq_probe_metrics) that probe launches add
     to; `collect()` reads them, `fold_into()` adds them to a host KeyQueryMetrics."""
