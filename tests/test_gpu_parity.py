@@ -630,6 +630,36 @@ def test_bloom_monolithic_duplicate_keys(oracle, amq, torch):
     assert_same(plan, out, ref)
 
 
+def test_bloom_monolithic_raw_key_overflow_above_12_bits(oracle, amq, torch):
+    """64 bits/key (k = 32): 16-byte keys are partitioned as keys and hashed by the tile build,
+    so the overflow lists hold raw keys, which bloom_overflow hashes again.  One filter of 2,561
+    blocks (two tiles) from 20,488 distinct keys chosen so that every one falls in tile 0: the
+    partition runs 21 workgroups of at most 976 keys, a (tile, workgroup) region holds 640
+    (part_geom: mean 488 + 6 sigma + 16, in sixteens), so about 7,000 keys reach the filter
+    through the overflow lists alone and every bit of theirs is set by bloom_overflow.
+    The library does not report its overflow counts: the figures below restate mono_wg_items and
+    part_geom (tkv_amq_kernels.hip) and must move with them, or the test stops reaching the
+    overflow pass without failing."""
+    import xxhash
+    n, bpk = 2561 * 8, 64
+    rng = np.random.default_rng(15)
+    cand = rng.integers(0, 256, (27000, 16), dtype=np.uint8)
+    seed0 = _bloom_seed(0)
+    keep = [i for i in range(len(cand)) if (xxhash.xxh64_intdigest(cand[i].tobytes(), seed0) * 2561) >> 64 < 2048]
+    assert len(keep) >= n
+    keys = np.ascontiguousarray(cand[keep[:n]])
+    wgs = -(-n // 1024)                      # 1,024 keys per workgroup aimed at for a filter this small
+    per, mean = -(-n // wgs), -(-n // wgs) / 2
+    cap = (int(mean + 6.0 * mean ** 0.5 + 16.0) + 15) & ~15
+    assert (wgs, per, cap) == (21, 976, 640) and per > cap
+    ref = oracle_per_segment(oracle, 0, keys, [n], bpk)
+    plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), [n], bpk)
+    assert int(plan.segs[0]["hash_count"]) == 32 and int(plan.segs[0]["n_blocks"]) == 2561
+    r, _ = amq.filters.build_route(plan, 16, False)
+    assert r.route == amq.abi.ROUTE_TILED_KEYS
+    assert_same(plan, out, ref)
+
+
 def sampled_tiles_equal_oracle(oracle, out, n, bpk, seed, n_random=6, extra_tiles=(), whole=False):
     """The header and sampled tiles of a GPU-built monolithic filter over gen_keys16(seed, 0, n)
     (the first, the last, six seeded-random ones and `extra_tiles`, e.g. both sides of every

@@ -162,6 +162,33 @@ def test_window_one_filter(oracle, amq, torch, n, bpk, shape):
     assert_same(plan, out, ref)
 
 
+@pytest.mark.parametrize("shape", ["var", "k40"])
+@pytest.mark.parametrize("n,bpk", [(2561 * 8, 64), (2561 * 32, 16)])
+def test_window_long_keys_generic_k(oracle, amq, torch, n, bpk, shape):
+    """The packed wave's re-hash of keys moved as their index (win_insert) with keys of 32
+    bytes and more at hash counts other than 7 / 8: one filter of 2,561 blocks, one block past
+    an LDS image, so two windows, at k = 32 and k = 11; variable-length keys of 20-47 bytes (both
+    hash branches in one wave) and 40-byte keys (the per-seed long hash alone).  The key counts
+    (20,488 and 81,952) are the fewest that make 2,561 blocks at these bits per key."""
+    rng = np.random.default_rng(n + bpk)
+    offs = None
+    if shape == "var":
+        lens = rng.integers(20, 48, n)
+        keys, stride = rng.integers(0, 256, int(lens.sum()), dtype=np.uint8), 0
+        offs = np.zeros(n + 1, np.int64)
+        offs[1:] = np.cumsum(lens)
+    else:
+        keys, stride = rng.integers(0, 256, (n, 40), dtype=np.uint8), 40
+    plan, out = gpu_build(amq, torch, 0, torch.from_numpy(keys).cuda(), [n], bpk,
+                          offsets_t=None if offs is None else torch.from_numpy(offs).cuda())
+    assert int(plan.segs[0]["hash_count"]) == (32 if bpk == 64 else 11)
+    r, _ = routes(amq, plan, stride, offs is not None)
+    assert r.route == amq.abi.ROUTE_WINDOW and r.windows == 2
+    ref = oracle_per_segment(oracle, 0, keys, [n], bpk, stride=stride,
+                             offsets=None if offs is None else offs.astype(np.uint64))
+    assert_same(plan, out, ref)
+
+
 def test_window_without_workspace_one_part(oracle, amq, torch):
     """tkv_amq_build with no workspace: one part per leaf, windows written straight into the
     filters (no merge)."""

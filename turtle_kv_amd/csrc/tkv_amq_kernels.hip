@@ -6,6 +6,8 @@
 //                        lane rounds shared), bits set in an LDS image of the whole filter with
 //                        ds_or_b32, image written out with 16-byte coalesced stores.  Other key
 //                        shapes: 24-byte lanes, or XxhShort for any key under 32 bytes.
+//   Bloom hash           every Bloom kernel hashes through one hasher type per key shape (Bloom16,
+//                        BloomFixed<L>, BloomShort, BloomLong); they and bloom_h0_at name the seed table.
 //   bloom_part_* / bloom_tile   one filter larger than LDS (the monolithic variant, and a rank's
 //                        tile range of a hash-range sharded filter): each key hashed once into
 //                        a 12-byte bit record, ranked in its 128 KiB tile's run by an LDS
@@ -117,6 +119,95 @@ __device__ inline uint64_t hash_key(const uint8_t* keys, const uint64_t* offs, u
   return xxh64_bytes(p, len, seed);
 }
 
+// ---- Bloom hash in device code: the frozen spec, down to bloom_h0_at, and nowhere else ----
+// A Bloom hasher is a key shape's XXH64 state paired with its column of the seed table.  h0():
+// the 64-bit hash for seed 0 (block = bloom_block(h0, n_blocks), bit 0 = h0 & kBloomBitMask).
+// bit(j): a value whose low 9 bits are bit index j; ITS HIGH BITS ARE UNSPECIFIED: lds_set_bit
+// ignores them, every other consumer masks with kBloomBitMask where it takes the value.
+// kBloomShared: seed-independent work is done once per key, so a compile-time hash count is
+// unrolled; a long key always loops.  The helpers are always_inline: a site compiles as code in place.
+constexpr uint32_t kBloomBitMask = 511u;
+#define TKV_INLINE __device__ __attribute__((always_inline)) inline
+
+TKV_INLINE uint64_t bloom_block(uint64_t h0, uint32_t n_blocks) { return __umul64hi(h0, (uint64_t)n_blocks); }
+
+struct Bloom16 : Xxh16 {  // 16-byte keys
+  TKV_INLINE explicit Bloom16(const uint4& v) : Xxh16((uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32)) {}
+  TKV_INLINE Bloom16() : Xxh16() {}  // a state moved between lanes or parked: set rk1, k2
+  TKV_INLINE uint64_t h0() const { return finish(c_bloom.rhinit16[0]); }
+  TKV_INLINE uint32_t bit(uint32_t j) const { return finish_lo9(c_bloom.rhinit16[j]); }
+};
+
+template <int L>
+struct BloomFixed : XxhFixed<L> {  // L-byte keys, 8-byte aligned
+  TKV_INLINE explicit BloomFixed(const uint64_t (&lanes)[L / 8]) : XxhFixed<L>(lanes) {}
+  TKV_INLINE BloomFixed() : XxhFixed<L>() {}  // a moved state: set rk0, k[]
+  TKV_INLINE uint64_t h0() const { return this->finish(xxh_fixed_rc<L>(c_bloom.seed[0])); }
+  TKV_INLINE uint32_t bit(uint32_t j) const { return this->finish_lo9(xxh_fixed_rc<L>(c_bloom.seed[j])); }
+};
+
+struct BloomShort : XxhShort {  // any key under 32 bytes
+  using XxhShort::XxhShort;
+  TKV_INLINE uint64_t h0() const { return finish(c_bloom.seed_p5[0]); }
+  TKV_INLINE uint32_t bit(uint32_t j) const { return finish_lo9(c_bloom.seed_p5[j]); }
+};
+
+struct BloomLong {  // 32 bytes and more: every hash reads the whole key
+  const uint8_t* p;
+  uint64_t len;  // (64-bit, as xxh64_bytes takes it)
+  TKV_INLINE uint64_t h0() const { return xxh64_bytes(p, len, c_bloom.seed[0]); }
+  TKV_INLINE uint32_t bit(uint32_t j) const { return (uint32_t)xxh64_bytes(p, len, c_bloom.seed[j]); }
+};
+
+template <typename H>
+constexpr bool kBloomShared = !std::is_same_v<H, BloomLong>;
+
+// The one ladder: sink(j, bit(j)) for j = 1 .. k - 1.  K != 0: the hash count at compile time
+// (7 / 8, the counts at 10 / 12 bits per key), unrolled; K == 0: the run-time k.
+template <int K, typename H, typename Sink>
+TKV_INLINE void bloom_ladder(const H& x, uint32_t k, Sink&& sink)
+{
+  if constexpr (K != 0 && kBloomShared<H>) {
+#pragma unroll
+    for (uint32_t j = 1; j < (uint32_t)K; ++j) sink(j, x.bit(j));
+  } else {
+    for (uint32_t j = 1; j < k; ++j) sink(j, x.bit(j));
+  }
+}
+
+// A record's NB (8, or a wide record's 16) bit indices: hash j below the hash count, else the
+// padding, b_0 in the first record and b_8 in the second.  K as in bloom_ladder.
+template <int K, int NB, typename H>
+TKV_INLINE void bloom_fill_bits(const H& x, uint64_t h0, uint32_t k, uint32_t (&b)[NB])
+{
+  b[0] = (uint32_t)h0 & kBloomBitMask;
+  auto fill = [&](uint32_t j) {
+    return (K != 0 ? j < (uint32_t)K : j < k) ? x.bit(j) & kBloomBitMask : b[j <= 8 ? 0 : 8];
+  };
+  if constexpr (kBloomShared<H>) {
+#pragma unroll
+    for (uint32_t j = 1; j < (uint32_t)NB; ++j) b[j] = fill(j);
+  } else {
+    for (uint32_t j = 1; j < (uint32_t)NB; ++j) b[j] = fill(j);
+  }
+}
+
+// Key i's seed-0 hash as hash_key finishes it: a short key with seed[0] + P5, where BloomShort
+// reads seed_p5[0] (the same value; the window build keeps hash_key's instructions).
+template <int MODE>
+TKV_INLINE uint64_t bloom_h0_at(const uint8_t* keys, const uint64_t* offs, uint32_t stride, uint64_t i)
+{ return hash_key<MODE>(keys, offs, stride, i, c_bloom.seed[0]); }
+
+// The short/long dispatch of a generic key shape: f(the hasher that matches key i's length)
+template <int MODE, typename F>
+TKV_INLINE auto with_bloom_key_at(const uint8_t* keys, const uint64_t* offs, uint32_t stride, uint64_t i, F&& f)
+{
+  uint32_t len;
+  const uint8_t* p = key_at<MODE>(keys, offs, stride, i, len);
+  if (len < 32) return f(BloomShort(p, len));
+  return f(BloomLong{p, len});
+}
+
 // Workgroup barrier for LDS hazards only: this wave's LDS operations are complete, its global
 // loads and stores stay in flight (__syncthreads() also drains vmcnt, stores included).
 __device__ inline void lds_barrier()
@@ -138,29 +229,31 @@ __device__ inline void lds_set_bit(uint32_t* blk, uint32_t bit)
   atomicOr(blk + word, 1u << (bit & 31));
 }
 
+// the same into a block of a filter in global memory (device-scope atomic); masks `bit` itself
+TKV_INLINE void global_set_bit(uint32_t* blk, uint32_t bit)
+{
+  bit &= kBloomBitMask;
+  atomicOr(blk + (bit >> 5), 1u << (bit & 31));
+}
+
+// Every bit of one hashed key into an LDS image whose first block is `first` (a tile image's)
+template <int K, bool kMask = false, typename H>
+TKV_INLINE void bloom_insert(uint32_t* s_bits, uint32_t nb, uint32_t k, const H& x, uint32_t first = 0)
+{
+  const uint64_t h0 = x.h0();
+  uint32_t* blk = s_bits + 16 * ((uint32_t)bloom_block(h0, nb) - first);
+  lds_set_bit(blk, (uint32_t)h0 & kBloomBitMask);
+  bloom_ladder<K>(x, k, [&](uint32_t, uint32_t b) { lds_set_bit(blk, kMask ? b & kBloomBitMask : b); });
+}
+
 // Bloom insert of one fixed/variable-length key: keys under 32 bytes share the seed-independent
-// lane rounds over all k hashes (XxhShort); longer keys hash from scratch per seed.
+// lane rounds over all k hashes (BloomShort); longer keys hash from scratch per seed.
 template <int K, int MODE>
 __device__ inline void bloom_insert_any(uint32_t* s_bits, uint32_t nb, uint32_t k,
                                         const uint8_t* p, uint32_t len)
 {
-  if (len < 32) {
-    const XxhShort x(p, len);
-    const uint64_t h0 = x.finish(c_bloom.seed_p5[0]);
-    uint32_t* blk = s_bits + 16 * (uint32_t)__umul64hi(h0, (uint64_t)nb);
-    lds_set_bit(blk, (uint32_t)h0 & 511u);
-    if constexpr (K != 0) {
-#pragma unroll
-      for (uint32_t j = 1; j < (uint32_t)K; ++j) lds_set_bit(blk, x.finish_lo9(c_bloom.seed_p5[j]));
-    } else {
-      for (uint32_t j = 1; j < k; ++j) lds_set_bit(blk, x.finish_lo9(c_bloom.seed_p5[j]));
-    }
-  } else {
-    const uint64_t h0 = xxh64_bytes(p, len, c_bloom.seed[0]);
-    uint32_t* blk = s_bits + 16 * (uint32_t)__umul64hi(h0, (uint64_t)nb);
-    lds_set_bit(blk, (uint32_t)h0 & 511u);
-    for (uint32_t j = 1; j < k; ++j) lds_set_bit(blk, (uint32_t)xxh64_bytes(p, len, c_bloom.seed[j]) & 511u);
-  }
+  if (len < 32) bloom_insert<K>(s_bits, nb, k, BloomShort(p, len));
+  else bloom_insert<0, true>(s_bits, nb, k, BloomLong{p, len});  // (kMask: the parent's v_and stays)
 }
 
 __device__ inline void write_bloom_header(uint8_t* payload, const tkv_amq_segment& sg, int part)
@@ -208,24 +301,6 @@ __device__ inline void write_page_header(uint8_t* out, const tkv_amq_segment& sg
   reinterpret_cast<uint4*>(page)[part] = v;
 }
 
-// `first`: block index of s_bits[0] (0 for a whole leaf image; a tile's first block for the
-// monolithic build's tile images)
-template <int K>
-__device__ inline void bloom_insert16(uint32_t* s_bits, uint32_t nb, uint32_t k, const uint4& kv,
-                                      uint32_t first)
-{
-  const Xxh16 x((uint64_t)kv.x | ((uint64_t)kv.y << 32), (uint64_t)kv.z | ((uint64_t)kv.w << 32));
-  const uint64_t h0 = x.finish(c_bloom.rhinit16[0]);
-  uint32_t* blk = s_bits + 16 * ((uint32_t)__umul64hi(h0, (uint64_t)nb) - first);
-  lds_set_bit(blk, (uint32_t)h0 & 511u);
-  if constexpr (K != 0) {
-#pragma unroll
-    for (uint32_t j = 1; j < (uint32_t)K; ++j) lds_set_bit(blk, x.finish_lo9(c_bloom.rhinit16[j]));
-  } else {
-    for (uint32_t j = 1; j < k; ++j) lds_set_bit(blk, x.finish_lo9(c_bloom.rhinit16[j]));
-  }
-}
-
 template <int K, uint32_t NT = 256>
 __device__ inline void bloom_keys16_lds(const uint4* __restrict__ kp, uint32_t n, uint32_t nb,
                                         uint32_t k, uint32_t* s_bits, uint32_t first = 0)
@@ -242,7 +317,7 @@ __device__ inline void bloom_keys16_lds(const uint4* __restrict__ kp, uint32_t n
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t i = base + u * NT + tid;
-      if (i < n) bloom_insert16<K>(s_bits, nb, k, kv[u], first);
+      if (i < n) bloom_insert<K>(s_bits, nb, k, Bloom16(kv[u]), first);
     }
   }
 }
@@ -265,18 +340,7 @@ __device__ inline void bloom_keysL_lds(const uint64_t* __restrict__ kp, uint32_t
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (base + u * NT + tid < n) {
-        const XxhFixed<L> x(lanes[u]);
-        const uint64_t h0 = x.finish(xxh_fixed_rc<L>(c_bloom.seed[0]));
-        uint32_t* blk = s_bits + 16 * (uint32_t)__umul64hi(h0, (uint64_t)nb);
-        lds_set_bit(blk, (uint32_t)h0 & 511u);
-        if constexpr (K != 0) {
-#pragma unroll
-          for (uint32_t j = 1; j < (uint32_t)K; ++j)
-            lds_set_bit(blk, x.finish_lo9(xxh_fixed_rc<L>(c_bloom.seed[j])));
-        } else {
-          for (uint32_t j = 1; j < k; ++j)
-            lds_set_bit(blk, x.finish_lo9(xxh_fixed_rc<L>(c_bloom.seed[j])));
-        }
+        bloom_insert<K>(s_bits, nb, k, BloomFixed<L>(lanes[u]));
       }
     }
   }
@@ -442,16 +506,7 @@ __device__ inline void var_key_insert(uint32_t* s_bits, uint32_t nb, uint32_t k,
     uint64_t l[3];
     uint32_t t4, tb;
     key_win_parts(v.w, v.len, l, t4, tb);
-    const XxhShort x(v.len, l, t4, tb);
-    const uint64_t h0 = x.finish(c_bloom.seed_p5[0]);
-    uint32_t* blk = s_bits + 16 * (uint32_t)__umul64hi(h0, (uint64_t)nb);
-    lds_set_bit(blk, (uint32_t)h0 & 511u);
-    if constexpr (K != 0) {
-#pragma unroll
-      for (uint32_t j = 1; j < (uint32_t)K; ++j) lds_set_bit(blk, x.finish_lo9(c_bloom.seed_p5[j]));
-    } else {
-      for (uint32_t j = 1; j < k; ++j) lds_set_bit(blk, x.finish_lo9(c_bloom.seed_p5[j]));
-    }
+    bloom_insert<K>(s_bits, nb, k, BloomShort(v.len, l, t4, tb));
   } else {
     bloom_insert_any<K, kKeyVar>(s_bits, nb, k, v.p, v.len);
   }
@@ -707,15 +762,15 @@ __device__ inline uint32_t win_hash(const uint8_t* __restrict__ keys, const uint
 {
   uint64_t h0;
   if constexpr (MODE == kKey16) {
-    const Xxh16 x((uint64_t)kb.v.x | ((uint64_t)kb.v.y << 32), (uint64_t)kb.v.z | ((uint64_t)kb.v.w << 32));
-    h0 = x.finish(c_bloom.rhinit16[0]);
+    const Bloom16 x(kb.v);
+    h0 = x.h0();
     it.d[0] = lo32(x.rk1);
     it.d[1] = hi32(x.rk1);
     it.d[2] = lo32(x.k2);
     it.d[3] = hi32(x.k2);
   } else if constexpr (MODE == kKey24) {
-    const XxhFixed<24> x(kb.w);
-    h0 = x.finish(xxh_fixed_rc<24>(c_bloom.seed[0]));
+    const BloomFixed<24> x(kb.w);
+    h0 = x.h0();
     it.d[0] = lo32(x.rk0);
     it.d[1] = hi32(x.rk0);
     it.d[2] = lo32(x.k[0]);
@@ -723,11 +778,11 @@ __device__ inline uint32_t win_hash(const uint8_t* __restrict__ keys, const uint
     it.d[4] = lo32(x.k[1]);
     it.d[5] = hi32(x.k[1]);
   } else {
-    h0 = hash_key<MODE>(keys, offs, stride, sg.key_begin + i, c_bloom.seed[0]);
+    h0 = bloom_h0_at<MODE>(keys, offs, stride, sg.key_begin + i);
     it.d[0] = i;
   }
-  it.d[WinItem<MODE>::N - 1] = ((uint32_t)h0 & 511u) << 12;
-  return (uint32_t)__umul64hi(h0, (uint64_t)sg.n_blocks);
+  it.d[WinItem<MODE>::N - 1] = ((uint32_t)h0 & kBloomBitMask) << 12;
+  return (uint32_t)bloom_block(h0, sg.n_blocks);
 }
 
 // the other k - 1 bits of a packed key, and bit 0
@@ -739,37 +794,37 @@ __device__ inline void win_insert(const uint8_t* __restrict__ keys, const uint64
   const uint32_t loc = it.d[WinItem<MODE>::N - 1];
   uint32_t* blk = s_bits + 16 * (loc & 0xfffu);
   lds_set_bit(blk, loc >> 12);
-  const uint32_t kk = K != 0 ? (uint32_t)K : k;
   if constexpr (MODE == kKey16) {
-    Xxh16 x;
+    Bloom16 x;
     x.rk1 = mk64(it.d[0], it.d[1]);
     x.k2 = mk64(it.d[2], it.d[3]);
     if constexpr (K != 0) {
 #pragma unroll
-      for (uint32_t j = 1; j < (uint32_t)K; ++j) lds_set_bit(blk, x.finish_lo9(c_bloom.rhinit16[j]));
+      for (uint32_t j = 1; j < (uint32_t)K; ++j) lds_set_bit(blk, x.bit(j));
     } else {
-      for (uint32_t j = 1; j < kk; ++j) lds_set_bit(blk, x.finish_lo9(c_bloom.rhinit16[j]));
+      for (uint32_t j = 1; j < k; ++j) lds_set_bit(blk, x.bit(j));
     }
   } else if constexpr (MODE == kKey24) {
-    XxhFixed<24> x;
+    BloomFixed<24> x;
     x.rk0 = mk64(it.d[0], it.d[1]);
     x.k[0] = mk64(it.d[2], it.d[3]);
     x.k[1] = mk64(it.d[4], it.d[5]);
     if constexpr (K != 0) {
 #pragma unroll
-      for (uint32_t j = 1; j < (uint32_t)K; ++j)
-        lds_set_bit(blk, x.finish_lo9(xxh_fixed_rc<24>(c_bloom.seed[j])));
+      for (uint32_t j = 1; j < (uint32_t)K; ++j) lds_set_bit(blk, x.bit(j));
     } else {
-      for (uint32_t j = 1; j < kk; ++j) lds_set_bit(blk, x.finish_lo9(xxh_fixed_rc<24>(c_bloom.seed[j])));
+      for (uint32_t j = 1; j < k; ++j) lds_set_bit(blk, x.bit(j));
     }
   } else {
     uint32_t len;
     const uint8_t* p = key_at<MODE>(keys, offs, stride, sg.key_begin + it.d[0], len);
+    const uint32_t kk = K != 0 ? (uint32_t)K : k;
     if (len < 32) {
-      const XxhShort x(p, len);
-      for (uint32_t j = 1; j < kk; ++j) lds_set_bit(blk, x.finish_lo9(c_bloom.seed_p5[j]));
+      const BloomShort x(p, len);
+      for (uint32_t j = 1; j < kk; ++j) lds_set_bit(blk, x.bit(j));
     } else {
-      for (uint32_t j = 1; j < kk; ++j) lds_set_bit(blk, (uint32_t)xxh64_bytes(p, len, c_bloom.seed[j]));
+      const BloomLong x{p, len};
+      for (uint32_t j = 1; j < kk; ++j) lds_set_bit(blk, x.bit(j));
     }
   }
 }
@@ -931,28 +986,14 @@ __global__ __launch_bounds__(256) void bloom_global_set(const uint8_t* __restric
     // leaves other than the oversize ones)
     if (sg.hash_count == 0 || i < sg.key_begin || i >= sg.key_begin + sg.n_keys) continue;
     uint32_t* words = reinterpret_cast<uint32_t*>(out + sg.out_offset + kBloomHeader);
-    uint64_t h0;
-    if constexpr (MODE == kKey16) {
-      const uint4 kv = reinterpret_cast<const uint4*>(keys)[i];
-      const Xxh16 x((uint64_t)kv.x | ((uint64_t)kv.y << 32), (uint64_t)kv.z | ((uint64_t)kv.w << 32));
-      h0 = x.finish(c_bloom.rhinit16[0]);
-      uint32_t* blk = words + 16 * (uint64_t)__umul64hi(h0, (uint64_t)sg.n_blocks);
-      const uint32_t b0 = (uint32_t)h0 & 511u;
-      atomicOr(blk + (b0 >> 5), 1u << (b0 & 31));
-      for (uint32_t j = 1; j < sg.hash_count; ++j) {
-        const uint32_t b = x.finish_lo9(c_bloom.rhinit16[j]) & 511u;
-        atomicOr(blk + (b >> 5), 1u << (b & 31));
-      }
-    } else {
-      h0 = hash_key<MODE>(keys, offs, stride, i, c_bloom.seed[0]);
-      uint32_t* blk = words + 16 * (uint64_t)__umul64hi(h0, (uint64_t)sg.n_blocks);
-      const uint32_t b0 = (uint32_t)h0 & 511u;
-      atomicOr(blk + (b0 >> 5), 1u << (b0 & 31));
-      for (uint32_t j = 1; j < sg.hash_count; ++j) {
-        const uint32_t b = (uint32_t)hash_key<MODE>(keys, offs, stride, i, c_bloom.seed[j]) & 511u;
-        atomicOr(blk + (b >> 5), 1u << (b & 31));
-      }
-    }
+    auto set = [&](const auto& x) {
+      const uint64_t h0 = x.h0();
+      uint32_t* blk = words + 16 * bloom_block(h0, sg.n_blocks);
+      global_set_bit(blk, (uint32_t)h0);
+      bloom_ladder<0>(x, sg.hash_count, [&](uint32_t, uint32_t b) { global_set_bit(blk, b); });
+    };
+    if constexpr (MODE == kKey16) set(Bloom16(reinterpret_cast<const uint4*>(keys)[i]));
+    else with_bloom_key_at<MODE>(keys, offs, stride, i, set);
   }
 }
 
@@ -1093,9 +1134,7 @@ inline PartGeom part_geom(uint64_t n_max, uint64_t n_exp, uint32_t n_tiles, uint
 
 __device__ inline uint32_t bloom_tile_of(const uint4& kv, uint32_t nb)
 {
-  const Xxh16 x((uint64_t)kv.x | ((uint64_t)kv.y << 32), (uint64_t)kv.z | ((uint64_t)kv.w << 32));
-  const uint64_t h0 = x.finish(c_bloom.rhinit16[0]);
-  return (uint32_t)__umul64hi(h0, (uint64_t)nb) >> kTileShift;
+  return (uint32_t)bloom_block(Bloom16(kv).h0(), nb) >> kTileShift;
 }
 
 // 24-byte keys (TurtleKV's default key size, 8-byte aligned) where the hash-once paths take
@@ -1114,9 +1153,7 @@ __device__ inline Key24 load_key24(const uint8_t* keys, uint32_t i)
 
 __device__ inline uint32_t bloom_tile_of(const Key24& kv, uint32_t nb)
 {
-  const XxhFixed<24> x(kv.w);
-  const uint64_t h0 = x.finish(xxh_fixed_rc<24>(c_bloom.seed[0]));
-  return (uint32_t)__umul64hi(h0, (uint64_t)nb) >> kTileShift;
+  return (uint32_t)bloom_block(BloomFixed<24>(kv.w).h0(), nb) >> kTileShift;
 }
 
 // key i of a 16- or 24-byte key array
@@ -1140,19 +1177,31 @@ __device__ inline uint32_t rec_tile(uint32_t w0, uint32_t w1, uint32_t w2)
   return (w0 >> 29) | ((w1 >> 27) << 3) | ((w2 >> 27) << 8);
 }
 
+// rec_pack's inverse: b[j]'s low 9 bits are b_j, the high bits unspecified as a hasher's bit(j)
+TKV_INLINE void rec_bits(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t (&b)[8])
+{
+  b[0] = w0 >> 11; b[1] = w0 >> 20;
+  b[2] = w1; b[3] = w1 >> 9; b[4] = w1 >> 18;
+  b[5] = w2; b[6] = w2 >> 9; b[7] = w2 >> 18;
+}
+
+// a record's first min(k, 8) bits into its block of a filter in global memory
+TKV_INLINE void rec_global_set(uint32_t* blk, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t k)
+{
+  uint32_t b[8];
+  rec_bits(w0, w1, w2, b);
+  const uint32_t kk = k < 8 ? k : 8u;
+  for (uint32_t j = 0; j < kk; ++j) global_set_bit(blk, b[j]);
+}
+
 // a 16-byte key's block in the filter and its k <= 8 bit indices (b_j = b_0 for j >= k)
 template <int K>
 __device__ inline uint32_t rec_hash_bits(const uint4& kv, uint32_t nb, uint32_t k, uint32_t (&b)[8])
 {
-  const Xxh16 x((uint64_t)kv.x | ((uint64_t)kv.y << 32), (uint64_t)kv.z | ((uint64_t)kv.w << 32));
-  const uint64_t h0 = x.finish(c_bloom.rhinit16[0]);
-  b[0] = (uint32_t)h0 & 511u;
-#pragma unroll
-  for (uint32_t j = 1; j < 8; ++j) {
-    if (K != 0 ? j < (uint32_t)K : j < k) b[j] = x.finish_lo9(c_bloom.rhinit16[j]) & 511u;
-    else b[j] = b[0];
-  }
-  return (uint32_t)__umul64hi(h0, (uint64_t)nb);
+  const Bloom16 x(kv);
+  const uint64_t h0 = x.h0();
+  bloom_fill_bits<K>(x, h0, k, b);
+  return (uint32_t)bloom_block(h0, nb);
 }
 
 // a 24-byte key's block and its bit indices (k > 8: the first eight; bloom_overflow sets the
@@ -1160,28 +1209,14 @@ __device__ inline uint32_t rec_hash_bits(const uint4& kv, uint32_t nb, uint32_t 
 template <int K>
 __device__ inline uint32_t rec_hash_bits(const Key24& kv, uint32_t nb, uint32_t k, uint32_t (&b)[8])
 {
-  const XxhFixed<24> x(kv.w);
-  const uint64_t h0 = x.finish(xxh_fixed_rc<24>(c_bloom.seed[0]));
-  b[0] = (uint32_t)h0 & 511u;
-#pragma unroll
-  for (uint32_t j = 1; j < 8; ++j) {
-    if (K != 0 ? j < (uint32_t)K : j < k) b[j] = x.finish_lo9(xxh_fixed_rc<24>(c_bloom.seed[j])) & 511u;
-    else b[j] = b[0];
-  }
-  return (uint32_t)__umul64hi(h0, (uint64_t)nb);
+  const BloomFixed<24> x(kv.w);
+  const uint64_t h0 = x.h0();
+  bloom_fill_bits<K>(x, h0, k, b);
+  return (uint32_t)bloom_block(h0, nb);
 }
 
 // 12-byte records per key: one up to k = 8, two (a wide record) up to k = 16, 0: none
 __host__ __device__ constexpr inline uint32_t bloom_rpk(uint32_t k) { return k == 0 || k > 16 ? 0u : (k <= 8 ? 1u : 2u); }
-
-// b_j of a key's NB (8 or 16) record indices: hash j below k, else the padding (b_0 in the
-// first record, b_8 in the second)
-template <int NB, typename F>
-__device__ inline void any_fill_bits(uint32_t k, uint32_t (&b)[NB], F&& hash_j)
-{
-#pragma unroll
-  for (uint32_t j = 1; j < (uint32_t)NB; ++j) b[j] = j < k ? hash_j(j) & 511u : b[j <= 8 ? 0 : 8];
-}
 
 // A key of any shape: its block and its NB bit indices (NB = 8: k <= 8; NB = 16: the two halves
 // of a wide record; NB = 0: the block alone, the route's count pass).  Under 32 bytes the
@@ -1200,28 +1235,19 @@ __device__ inline uint32_t any_hash_bits(const uint8_t* keys, const VarRsrc& vr,
     uint64_t l[3];
     uint32_t t4, tb;
     key_win_parts(kw, len, l, t4, tb);
-    const XxhShort x(len, l, t4, tb);
-    h0 = x.finish(c_bloom.seed_p5[0]);
-    if constexpr (NB != 0) {
-      b[0] = (uint32_t)h0 & 511u;
-      any_fill_bits<NB>(k, b, [&](uint32_t j) { return x.finish_lo9(c_bloom.seed_p5[j]); });
-    }
+    const BloomShort x(len, l, t4, tb);
+    h0 = x.h0();
+    if constexpr (NB != 0) bloom_fill_bits<0>(x, h0, k, b);
   } else if (len < 32) {
-    const XxhShort x(p, len);
-    h0 = x.finish(c_bloom.seed_p5[0]);
-    if constexpr (NB != 0) {
-      b[0] = (uint32_t)h0 & 511u;
-      any_fill_bits<NB>(k, b, [&](uint32_t j) { return x.finish_lo9(c_bloom.seed_p5[j]); });
-    }
+    const BloomShort x(p, len);
+    h0 = x.h0();
+    if constexpr (NB != 0) bloom_fill_bits<0>(x, h0, k, b);
   } else {
-    h0 = xxh64_bytes(p, len, c_bloom.seed[0]);
-    if constexpr (NB != 0) {
-      b[0] = (uint32_t)h0 & 511u;
-      for (uint32_t j = 1; j < (uint32_t)NB; ++j)
-        b[j] = j < k ? (uint32_t)xxh64_bytes(p, len, c_bloom.seed[j]) & 511u : b[j <= 8 ? 0 : 8];
-    }
+    const BloomLong x{p, len};
+    h0 = x.h0();
+    if constexpr (NB != 0) bloom_fill_bits<0>(x, h0, k, b);
   }
-  return (uint32_t)__umul64hi(h0, (uint64_t)nb);
+  return (uint32_t)bloom_block(h0, nb);
 }
 
 // the RPK records of a key from its block (tile `tile` of the records' build or part) and bits
@@ -2068,17 +2094,11 @@ __global__ __launch_bounds__(256) void bloom_route_ovf_apply(const tkv_amq_segme
   const uint32_t n = min(*reinterpret_cast<const uint32_t*>(cnt + (uint64_t)l * cnt_stride), cap);
   const uint4* list = reinterpret_cast<const uint4*>(ent + (uint64_t)l * ent_stride);
   uint32_t* words = reinterpret_cast<uint32_t*>(out + sg.out_offset + kBloomHeader);
-  const uint32_t kk = k < 8 ? k : 8u;
   for (uint32_t e = threadIdx.x; e < n; e += 256) {
     const uint4 x = list[e];
     if (x.w < p0 || x.w >= p1) continue;
     const uint64_t blk = ((uint64_t)x.w * q + rec_tile(x.x, x.y, x.z)) * kTileBlocks + (x.x & (kTileBlocks - 1));
-    const uint32_t b[8] = {x.x >> 11, x.x >> 20, x.y, x.y >> 9, x.y >> 18, x.z, x.z >> 9, x.z >> 18};
-    uint32_t* bw = words + 16ull * blk;
-    for (uint32_t j = 0; j < kk; ++j) {
-      const uint32_t bj = b[j] & 511u;
-      atomicOr(bw + (bj >> 5), 1u << (bj & 31u));
-    }
+    rec_global_set(words + 16ull * blk, x.x, x.y, x.z, k);
   }
 }
 
@@ -2093,7 +2113,8 @@ template <int K>
 __device__ inline void rec_insert(uint32_t* img, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t k)
 {
   uint32_t* blk = img + 16 * (w0 & (kTileBlocks - 1));
-  const uint32_t b[8] = {w0 >> 11, w0 >> 20, w1, w1 >> 9, w1 >> 18, w2, w2 >> 9, w2 >> 18};
+  uint32_t b[8];
+  rec_bits(w0, w1, w2, b);
 #pragma unroll
   for (uint32_t j = 0; j < 8; ++j)
     if (K != 0 ? j < (uint32_t)K : j < k) lds_set_bit(blk, b[j]);
@@ -2156,7 +2177,7 @@ __device__ void tile_body(const tkv_amq_segment& sg, const PartArgs& a, uint32_t
 #pragma unroll
     for (uint32_t v = 0; v < V; ++v) {
       if (q.i0 + v * 64 + lane >= q.c) continue;
-      if constexpr (RAW) bloom_insert16<0>(img, nb, k, make_uint4(q.x[v][0], q.x[v][1], q.x[v][2], q.x[v][3]), first);
+      if constexpr (RAW) bloom_insert<0>(img, nb, k, Bloom16(make_uint4(q.x[v][0], q.x[v][1], q.x[v][2], q.x[v][3])), first);
       else rec_insert<K>(img, q.x[v][0], q.x[v][1], q.x[v][2], k);
     }
   };
@@ -2280,40 +2301,26 @@ __device__ __attribute__((always_inline)) inline void overflow_run(const tkv_amq
     const uint32_t per = a.g.per;
     const uint32_t kb = min(n_items, w * per), ke = min(n_items, kb + per);
     for (uint32_t i = kb + threadIdx.x; i < ke; i += 256) {
-      const XxhFixed<24> x(load_key24(src, i).w);
-      const uint64_t h0 = x.finish(xxh_fixed_rc<24>(c_bloom.seed[0]));
-      const uint32_t blk = (uint32_t)__umul64hi(h0, (uint64_t)nb);
+      const BloomFixed<24> x(load_key24(src, i).w);
+      const uint32_t blk = (uint32_t)bloom_block(x.h0(), nb);
       if ((blk >> kTileShift) - a.tile0 >= a.g.n_tiles) continue;  // (outside the window)
       uint32_t* bw = words + 16ull * blk;
-      for (uint32_t j = 8; j < k; ++j) {
-        const uint32_t bj = x.finish_lo9(xxh_fixed_rc<24>(c_bloom.seed[j])) & 511u;
-        atomicOr(bw + (bj >> 5), 1u << (bj & 31u));
-      }
+      for (uint32_t j = 8; j < k; ++j) global_set_bit(bw, x.bit(j));
     }
   }
   for (uint32_t e = threadIdx.x; e < n; e += 256) {
     if (raw) {
-      const uint4 q = *reinterpret_cast<const uint4*>(list + 16ull * e);
-      const Xxh16 x((uint64_t)q.x | ((uint64_t)q.y << 32), (uint64_t)q.z | ((uint64_t)q.w << 32));
-      const uint64_t h0 = x.finish(c_bloom.rhinit16[0]);
-      uint32_t* bw = words + 16 * (uint64_t)__umul64hi(h0, (uint64_t)nb);
-      atomicOr(bw + ((h0 & 511u) >> 5), 1u << (h0 & 31u));
-      for (uint32_t j = 1; j < k; ++j) {
-        const uint32_t bj = x.finish_lo9(c_bloom.rhinit16[j]) & 511u;
-        atomicOr(bw + (bj >> 5), 1u << (bj & 31u));
-      }
+      const Bloom16 x(*reinterpret_cast<const uint4*>(list + 16ull * e));
+      const uint64_t h0 = x.h0();
+      uint32_t* bw = words + 16 * bloom_block(h0, nb);
+      global_set_bit(bw, (uint32_t)h0);
+      bloom_ladder<0>(x, k, [&](uint32_t, uint32_t b) { global_set_bit(bw, b); });
       continue;
     }
     // a record whose region was full (its tile relative to the build's first tile is in it)
     const uint3 r = *reinterpret_cast<const uint3*>(list + 12ull * e);
     const uint64_t blk = (uint64_t)(a.tile0 + rec_tile(r.x, r.y, r.z)) * kTileBlocks + (r.x & (kTileBlocks - 1));
-    const uint32_t b[8] = {r.x >> 11, r.x >> 20, r.y, r.y >> 9, r.y >> 18, r.z, r.z >> 9, r.z >> 18};
-    uint32_t* bw = words + 16ull * blk;
-    const uint32_t kk = k < 8 ? k : 8u;
-    for (uint32_t j = 0; j < kk; ++j) {
-      const uint32_t bj = b[j] & 511u;
-      atomicOr(bw + (bj >> 5), 1u << (bj & 31u));
-    }
+    rec_global_set(words + 16ull * blk, r.x, r.y, r.z, k);
   }
 }
 
@@ -2468,7 +2475,7 @@ constexpr uint32_t kProbeSlotWords = 20;
 // The block's four 16-byte loads are issued first and the remaining k-1 bit indices are
 // hashed while they are in flight; only then is the block staged in the lane's LDS slot.
 template <int K>
-__device__ inline uint32_t probe_block16(const Xxh16& x, uint64_t h0, const uint4* blk, uint4* slot,
+__device__ inline uint32_t probe_block16(const Bloom16& x, uint64_t h0, const uint4* blk, uint4* slot,
                                          uint32_t k_rt = K)
 {
   const uint4 b0 = blk[0], b1 = blk[1], b2 = blk[2], b3 = blk[3];
@@ -2476,9 +2483,8 @@ __device__ inline uint32_t probe_block16(const Xxh16& x, uint64_t h0, const uint
   uint32_t ok = 1;
   if constexpr (K > 0) {
     uint32_t bit[K];
-    bit[0] = (uint32_t)h0 & 511u;
-#pragma unroll
-    for (int j = 1; j < K; ++j) bit[j] = x.finish_lo9(c_bloom.rhinit16[j]) & 511u;
+    bit[0] = (uint32_t)h0 & kBloomBitMask;
+    bloom_ladder<K>(x, K, [&](uint32_t j, uint32_t b) { bit[j] = b & kBloomBitMask; });
     slot[0] = b0;
     slot[1] = b1;
     slot[2] = b2;
@@ -2490,10 +2496,10 @@ __device__ inline uint32_t probe_block16(const Xxh16& x, uint64_t h0, const uint
     slot[1] = b1;
     slot[2] = b2;
     slot[3] = b3;
-    uint32_t b = (uint32_t)h0 & 511u;
+    uint32_t b = (uint32_t)h0 & kBloomBitMask;
     ok &= slot32[b >> 5] >> (b & 31);
     for (uint32_t j = 1; j < k_rt; ++j) {
-      b = x.finish_lo9(c_bloom.rhinit16[j]) & 511u;
+      b = x.bit(j) & kBloomBitMask;
       ok &= slot32[b >> 5] >> (b & 31);
     }
   }
@@ -2571,10 +2577,10 @@ __device__ inline uint32_t bloom_probe_item(const uint8_t* __restrict__ filters,
     // test, so they are issued before it: one dependent chain qseg -> descriptor -> block
     const uint4 kv = load_nt16(q + 16 * i);
     const ProbeDesc d = load_probe_desc(segs, sidx, n_segs);
-    const Xxh16 x((uint64_t)kv.x | ((uint64_t)kv.y << 32), (uint64_t)kv.z | ((uint64_t)kv.w << 32));
-    const uint64_t h0 = x.finish(c_bloom.rhinit16[0]);
+    const Bloom16 x(kv);
+    const uint64_t h0 = x.h0();
     const uint4* blk = reinterpret_cast<const uint4*>(filters + d.out_offset + kBloomHeader +
-                                                      64 * __umul64hi(h0, (uint64_t)d.n_blocks));
+                                                      64 * bloom_block(h0, d.n_blocks));
     // hash_count 0: no filter page => reject_page returns kUnknown => cannot reject
     uint32_t cls = d.hash_count == 0 ? kNoFilter : kChecked;
     if constexpr (kOpts) {
@@ -2594,22 +2600,23 @@ __device__ inline uint32_t bloom_probe_item(const uint8_t* __restrict__ filters,
     uint32_t len;
     const uint8_t* p = key_at<MODE>(q, qoffs, stride, i, len);
     if (len < 32) {  // seed-independent lane rounds shared by the k hashes
-      const XxhShort x(p, len);
-      const uint64_t h0 = x.finish(c_bloom.seed_p5[0]);
-      const uint64_t* blk = reinterpret_cast<const uint64_t*>(words + 64 * __umul64hi(h0, (uint64_t)d.n_blocks));
-      uint32_t b = (uint32_t)h0 & 511u;
+      const BloomShort x(p, len);
+      const uint64_t h0 = x.h0();
+      const uint64_t* blk = reinterpret_cast<const uint64_t*>(words + 64 * bloom_block(h0, d.n_blocks));
+      uint32_t b = (uint32_t)h0 & kBloomBitMask;
       ok &= (uint32_t)(blk[b >> 6] >> (b & 63));
       for (uint32_t j = 1; j < d.hash_count; ++j) {
-        b = x.finish_lo9(c_bloom.seed_p5[j]) & 511u;
+        b = x.bit(j) & kBloomBitMask;
         ok &= (uint32_t)(blk[b >> 6] >> (b & 63));
       }
     } else {
-      const uint64_t h0 = xxh64_bytes(p, len, c_bloom.seed[0]);
-      const uint64_t* blk = reinterpret_cast<const uint64_t*>(words + 64 * __umul64hi(h0, (uint64_t)d.n_blocks));
-      uint32_t b = (uint32_t)h0 & 511u;
+      const BloomLong x{p, len};
+      const uint64_t h0 = x.h0();
+      const uint64_t* blk = reinterpret_cast<const uint64_t*>(words + 64 * bloom_block(h0, d.n_blocks));
+      uint32_t b = (uint32_t)h0 & kBloomBitMask;
       ok &= (uint32_t)(blk[b >> 6] >> (b & 63));
       for (uint32_t j = 1; j < d.hash_count; ++j) {
-        b = (uint32_t)xxh64_bytes(p, len, c_bloom.seed[j]) & 511u;
+        b = x.bit(j) & kBloomBitMask;
         ok &= (uint32_t)(blk[b >> 6] >> (b & 63));
       }
     }
@@ -4661,21 +4668,20 @@ __global__ __launch_bounds__(256) void bloom_hash_kernel(const uint8_t* __restri
   uint8_t* rec = out + i * bloom_query_stride(k_max);
   uint16_t* bits = reinterpret_cast<uint16_t*>(rec + 8);
   if constexpr (MODE == kKey16) {
-    const uint4 kv = load_nt16(q + 16 * i);
-    const Xxh16 x((uint64_t)kv.x | ((uint64_t)kv.y << 32), (uint64_t)kv.z | ((uint64_t)kv.w << 32));
-    *reinterpret_cast<uint64_t*>(rec) = x.finish(c_bloom.rhinit16[0]);
-    for (uint32_t j = 1; j < k_max; ++j) bits[j - 1] = (uint16_t)(x.finish_lo9(c_bloom.rhinit16[j]) & 511u);
+    const Bloom16 x(load_nt16(q + 16 * i));
+    *reinterpret_cast<uint64_t*>(rec) = x.h0();
+    for (uint32_t j = 1; j < k_max; ++j) bits[j - 1] = (uint16_t)(x.bit(j) & kBloomBitMask);
   } else {
     uint32_t len;
     const uint8_t* p = key_at<MODE>(q, qoffs, stride, i, len);
     if (len < 32) {
-      const XxhShort x(p, len);
-      *reinterpret_cast<uint64_t*>(rec) = x.finish(c_bloom.seed_p5[0]);
-      for (uint32_t j = 1; j < k_max; ++j) bits[j - 1] = (uint16_t)(x.finish_lo9(c_bloom.seed_p5[j]) & 511u);
+      const BloomShort x(p, len);
+      *reinterpret_cast<uint64_t*>(rec) = x.h0();
+      for (uint32_t j = 1; j < k_max; ++j) bits[j - 1] = (uint16_t)(x.bit(j) & kBloomBitMask);
     } else {
-      *reinterpret_cast<uint64_t*>(rec) = xxh64_bytes(p, len, c_bloom.seed[0]);
-      for (uint32_t j = 1; j < k_max; ++j)
-        bits[j - 1] = (uint16_t)(xxh64_bytes(p, len, c_bloom.seed[j]) & 511u);
+      const BloomLong x{p, len};
+      *reinterpret_cast<uint64_t*>(rec) = x.h0();
+      for (uint32_t j = 1; j < k_max; ++j) bits[j - 1] = (uint16_t)(x.bit(j) & kBloomBitMask);
     }
   }
 }
@@ -4710,16 +4716,16 @@ __global__ __launch_bounds__(256) void bloom_probe_hashed(const uint8_t* __restr
     } else {
       const uint16_t* bits = reinterpret_cast<const uint16_t*>(rec + 8);
       const uint4* blk = reinterpret_cast<const uint4*>(filters + d.out_offset + kBloomHeader +
-                                                        64 * __umul64hi(h0, (uint64_t)d.n_blocks));
+                                                        64 * bloom_block(h0, d.n_blocks));
       const uint4 b0 = blk[0], b1 = blk[1], b2 = blk[2], b3 = blk[3];
       slot[0] = b0;
       slot[1] = b1;
       slot[2] = b2;
       slot[3] = b3;
-      uint32_t bit = (uint32_t)h0 & 511u;
+      uint32_t bit = (uint32_t)h0 & kBloomBitMask;
       uint32_t ok = slot32[bit >> 5] >> (bit & 31);
       for (uint32_t j = 1; j < d.hash_count; ++j) {
-        bit = bits[j - 1];
+        bit = bits[j - 1];  // (cached masked)
         ok &= slot32[bit >> 5] >> (bit & 31);
       }
       r = (ok & 1u) | (kChecked << 1);
@@ -4859,7 +4865,7 @@ __device__ inline BloomEntry16 bloom_entry16_fetch(const uint8_t* __restrict__ f
   }
   f.k_cls = d.hash_count | (cls << 16);
   f.blk = reinterpret_cast<const uint4*>(filters + d.out_offset + kBloomHeader +
-                                         64 * __umul64hi(h0, (uint64_t)d.n_blocks));
+                                         64 * bloom_block(h0, d.n_blocks));
   return f;
 }
 
@@ -4868,12 +4874,12 @@ __device__ inline BloomEntry16 bloom_entry16_fetch(const uint8_t* __restrict__ f
 // hashes finishes indices 8.. again from the shared lane rounds (finish_lo9), per entry.
 struct BloomBits16 {
   uint32_t w[3];
-  __device__ inline explicit BloomBits16(const Xxh16& x)
+  __device__ inline explicit BloomBits16(const Bloom16& x)
   {
     w[0] = w[1] = w[2] = 0;
 #pragma unroll
     for (int j = 1; j < 8; ++j)
-      w[(j - 1) / 3] |= (x.finish_lo9(c_bloom.rhinit16[j]) & 511u) << (9 * ((j - 1) % 3));
+      w[(j - 1) / 3] |= (x.bit(j) & kBloomBitMask) << (9 * ((j - 1) % 3));
   }
   // `zero` is 0 at run time, but comes from the entry, so that the unpacking stays in the loop
   // over the path: hoisted out of it, every index is held as an LDS address and a shift, two
@@ -4919,16 +4925,16 @@ __device__ inline uint32_t bloom_entry16_test(uint64_t h0, const BloomBits16& bi
     slot[2] = b2;
     slot[3] = b3;
     const uint32_t k = f.k();
-    uint32_t bit = (uint32_t)h0 & 511u;
+    uint32_t bit = (uint32_t)h0 & kBloomBitMask;
     // (class < 4 and hash_count < 65536: bit 31 of k_cls is never set)
     ok = bloom_bits16_and<1>(bits, slot32, k, f.k_cls >> 31, slot32[bit >> 5] >> (bit & 31));
     if (k > 8) {
       const uint4 xs = slot[4];
-      Xxh16 x;
+      Bloom16 x;
       x.rk1 = (uint64_t)xs.x | ((uint64_t)xs.y << 32);
       x.k2 = (uint64_t)xs.z | ((uint64_t)xs.w << 32);
       for (uint32_t j = 8; j < k; ++j) {
-        bit = x.finish_lo9(c_bloom.rhinit16[j]) & 511u;
+        bit = x.bit(j) & kBloomBitMask;
         ok &= slot32[bit >> 5] >> (bit & 31);
       }
     }
@@ -4950,8 +4956,8 @@ __device__ inline uint32_t bloom_entry_test(const uint8_t* __restrict__ filters,
     if (!page_id_matches(filters + d.out_offset, 16, page_ids, ent)) return 1u | (kIdMismatch << 1);
   }
   const uint64_t* blk = reinterpret_cast<const uint64_t*>(filters + d.out_offset + kBloomHeader +
-                                                          64 * __umul64hi(h0, (uint64_t)d.n_blocks));
-  uint32_t b = (uint32_t)h0 & 511u;
+                                                          64 * bloom_block(h0, d.n_blocks));
+  uint32_t b = (uint32_t)h0 & kBloomBitMask;
   uint32_t ok = (uint32_t)(blk[b >> 6] >> (b & 63));
   for (uint32_t j = 1; j < d.hash_count; ++j) {
     b = bit_of(j, d.hash_count);
@@ -5000,8 +5006,8 @@ __global__ __launch_bounds__(256, (MODE == kKey16 && !kOpts ? 8 : 4)) void path_
         }
       } else if constexpr (MODE == kKey16) {
         const uint4 kv = load_nt16(a.q + 16 * i);
-        const Xxh16 x((uint64_t)kv.x | ((uint64_t)kv.y << 32), (uint64_t)kv.z | ((uint64_t)kv.w << 32));
-        const uint64_t h0 = x.finish(c_bloom.rhinit16[0]);
+        const Bloom16 x(kv);
+        const uint64_t h0 = x.h0();
         const BloomBits16 bits(x);
         bloom_entry16_park(x, slot);
         BloomEntry16 cur = bloom_entry16_fetch<kOpts>(a.filters, a.segs, a.n_segs, leaf, h0,
@@ -5016,38 +5022,30 @@ __global__ __launch_bounds__(256, (MODE == kKey16 && !kOpts ? 8 : 4)) void path_
           cur = nxt;
         }
       } else {
-        uint32_t len;
-        const uint8_t* p = key_at<MODE>(a.q, a.qoffs, a.stride, i, len);
-        if (len < 32) {  // seed-independent lane rounds shared by every hash of every filter
-          const XxhShort x(p, len);
-          const uint64_t h0 = x.finish(c_bloom.seed_p5[0]);
+        with_bloom_key_at<MODE>(a.q, a.qoffs, a.stride, i, [&](const auto& x) {
+          const uint64_t h0 = x.h0();
+          // Under 32 bytes the seed-independent lane rounds are shared by every hash of every
+          // filter.  A longer key's every hash reads the whole key: bit index j is computed when
+          // the first filter with more than j hashes comes by, and kept in the lane's LDS slot.
+          [[maybe_unused]] uint16_t* cache = reinterpret_cast<uint16_t*>(slot);
+          [[maybe_unused]] uint32_t have = 1;
+          auto bit_of = [&](uint32_t j, [[maybe_unused]] uint32_t k) {
+            if constexpr (kBloomShared<std::decay_t<decltype(x)>>) {
+              return x.bit(j) & kBloomBitMask;
+            } else {
+              for (const uint32_t want = min(k, kMaxBloomHashes); have < want; ++have)
+                cache[have] = (uint16_t)(x.bit(have) & kBloomBitMask);
+              return (uint32_t)cache[min(j, kMaxBloomHashes - 1)];
+            }
+          };
           for (uint32_t ent = b; ent < e; ++ent) {
             const uint32_t leaf1 = ent + 1 < e ? a.path_leaf[ent + 1] : 0u;
-            const uint32_t r = bloom_entry_test<kOpts>(
-                a.filters, a.segs, a.n_segs, leaf, h0, opts.d_query_page_id, ent,
-                [&](uint32_t j, uint32_t) { return x.finish_lo9(c_bloom.seed_p5[j]) & 511u; });
+            const uint32_t r = bloom_entry_test<kOpts>(a.filters, a.segs, a.n_segs, leaf, h0,
+                                                       opts.d_query_page_id, ent, bit_of);
             wk.record<kOpts>(a, opts, t, r, ent - b, ent);
             leaf = leaf1;
           }
-        } else {
-          // every hash reads the whole key: bit index j is computed when the first filter
-          // with more than j hashes comes by, and kept in the lane's LDS slot
-          uint16_t* cache = reinterpret_cast<uint16_t*>(slot);
-          const uint64_t h0 = xxh64_bytes(p, len, c_bloom.seed[0]);
-          uint32_t have = 1;
-          for (uint32_t ent = b; ent < e; ++ent) {
-            const uint32_t leaf1 = ent + 1 < e ? a.path_leaf[ent + 1] : 0u;
-            const uint32_t r = bloom_entry_test<kOpts>(
-                a.filters, a.segs, a.n_segs, leaf, h0, opts.d_query_page_id, ent,
-                [&](uint32_t j, uint32_t k) {
-                  for (const uint32_t want = min(k, kMaxBloomHashes); have < want; ++have)
-                    cache[have] = (uint16_t)(xxh64_bytes(p, len, c_bloom.seed[have]) & 511u);
-                  return (uint32_t)cache[min(j, kMaxBloomHashes - 1)];
-                });
-            wk.record<kOpts>(a, opts, t, r, ent - b, ent);
-            leaf = leaf1;
-          }
-        }
+        });
       }
     }
     if (live) a.mask[i] = wk.mask;
