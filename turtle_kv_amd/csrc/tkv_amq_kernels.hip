@@ -236,13 +236,28 @@ TKV_INLINE void global_set_bit(uint32_t* blk, uint32_t bit)
   atomicOr(blk + (bit >> 5), 1u << (bit & 31));
 }
 
-// Every bit of one hashed key into an LDS image whose first block is `first` (a tile image's)
+// LDS byte addresses (the low word of a generic pointer to LDS is its LDS address), and the
+// pointer of one
+typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
+__device__ inline uint32_t lds_addr(const void* p)
+{
+  return (uint32_t)reinterpret_cast<uintptr_t>(p);
+}
+TKV_INLINE uint32_t* lds_ptr(uint32_t a) { return (uint32_t*)reinterpret_cast<lds_u32_t*>((uintptr_t)a); }
+
+// Every bit of one hashed key into an LDS image whose first block is `first` (a tile image's).
+// The block is below 2^32 and the image base is a 32-bit LDS address, so the block's address is
+// one shift-add (spelled in 64 bits the compiler keeps a 64-bit shift and a mask); `first` moves
+// the wave-uniform base, not the block.  Bit 0 goes in unmasked, as the ladder's bits do.
 template <int K, bool kMask = false, typename H>
 TKV_INLINE void bloom_insert(uint32_t* s_bits, uint32_t nb, uint32_t k, const H& x, uint32_t first = 0)
 {
   const uint64_t h0 = x.h0();
-  uint32_t* blk = s_bits + 16 * ((uint32_t)bloom_block(h0, nb) - first);
-  lds_set_bit(blk, (uint32_t)h0 & kBloomBitMask);
+  uint32_t block = (uint32_t)bloom_block(h0, nb);
+  // (opaque: LLVM otherwise folds the shift into the 64-bit product, v_alignbit 26 + v_and + v_add)
+  asm("" : "+v"(block));
+  uint32_t* blk = lds_ptr((block << 6) + (lds_addr(s_bits) - (first << 6)));
+  lds_set_bit(blk, (uint32_t)h0);
   bloom_ladder<K>(x, k, [&](uint32_t, uint32_t b) { lds_set_bit(blk, kMask ? b & kBloomBitMask : b); });
 }
 
@@ -301,13 +316,57 @@ __device__ inline void write_page_header(uint8_t* out, const tkv_amq_segment& sg
   reinterpret_cast<uint4*>(page)[part] = v;
 }
 
+// A T at a wave-uniform address plus a 32-bit lane offset, loaded in the scalar-base form (no
+// per-load VALU address arithmetic).  The base is pinned to an SGPR pair first: left transparent,
+// the loop optimiser folds the lane offset into it and advances a 64-bit VGPR address with two
+// v_add_co per load.  The lane offset has to be defined in the loop body as well (an empty asm on
+// the loop-carried variable, no instruction): instruction selection works per basic block and
+// sees the 32-bit offset's zero-extension only there; hoisted, it costs a v_lshl_add_u64 per load.
+// These asms, the one in bloom_insert and the leaf loops' sched_barrier hold an instruction form
+// no test sees: after a compiler update rerun the check in profiles/leaf_loop/README.md
+// ("After a ROCm update"; tools/isa_loops.py: 972 / 1,096 and 618 / 696 v_* per full-chunk loop).
+TKV_INLINE uint64_t sgpr_addr(const uint8_t* base)
+{
+  uint64_t a = reinterpret_cast<uint64_t>(base);
+  asm("" : "+s"(a));
+  return a;
+}
+
+template <typename T>
+TKV_INLINE T load_sbase(uint64_t sbase, uint32_t lane_off, uint32_t imm = 0)
+{
+  return *reinterpret_cast<const __attribute__((address_space(1))) T*>(sbase + lane_off + imm);
+}
+
 template <int K, uint32_t NT = 256>
 __device__ inline void bloom_keys16_lds(const uint4* __restrict__ kp, uint32_t n, uint32_t nb,
-                                        uint32_t k, uint32_t* s_bits, uint32_t first = 0)
+                                        uint32_t k, uint32_t* s_bits)
 {
   const uint32_t tid = threadIdx.x;
   constexpr int U = 4;  // 4 x 16-byte loads in flight per lane
-  for (uint32_t base = 0; base < n; base += NT * U) {
+  constexpr uint32_t C = NT * U;
+  // Full chunks (all C keys present): no guards; key u of a lane is at a wave-uniform base, advanced
+  // per chunk on the scalar unit, plus the lane's byte offset, computed once.  (u * NT * 16 is past
+  // a global load's 13-bit immediate: one scalar base per u.)  kp is the same in every lane: the
+  // callers derive it from the leaf's segment and the workgroup's part.
+  const uint8_t* cb = reinterpret_cast<const uint8_t*>(kp);
+  uint32_t lane_off = tid * 16;
+  uint32_t base = 0;
+  for (; n - base >= C; base += C, cb += C * 16) {
+    asm volatile("" : "+v"(lane_off));  // (see load_sbase)
+    uint4 kv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const u32x4_t v = load_sbase<u32x4_t>(sgpr_addr(cb + u * NT * 16), lane_off);
+      kv[u] = uint4{v.x, v.y, v.z, v.w};
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      bloom_insert<K>(s_bits, nb, k, Bloom16(kv[u]));
+      __builtin_amdgcn_sched_barrier(0);  // one key at a time: interleaved, four keys take 93 VGPRs
+    }
+  }
+  if (base < n) {  // the tail: under C keys, each guarded
     uint4 kv[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -317,7 +376,7 @@ __device__ inline void bloom_keys16_lds(const uint4* __restrict__ kp, uint32_t n
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t i = base + u * NT + tid;
-      if (i < n) bloom_insert<K>(s_bits, nb, k, Bloom16(kv[u]), first);
+      if (i < n) bloom_insert<K>(s_bits, nb, k, Bloom16(kv[u]));
     }
   }
 }
@@ -329,7 +388,27 @@ __device__ inline void bloom_keysL_lds(const uint64_t* __restrict__ kp, uint32_t
   constexpr int N = L / 8;
   const uint32_t tid = threadIdx.x;
   constexpr int U = 2;
-  for (uint32_t base = 0; base < n; base += NT * U) {
+  constexpr uint32_t C = NT * U;
+  // full chunks as in bloom_keys16_lds: scalar bases, one lane offset, no guards or clamps
+  const uint8_t* cb = reinterpret_cast<const uint8_t*>(kp);
+  uint32_t lane_off = tid * L;
+  uint32_t base = 0;
+  for (; n - base >= C; base += C, cb += C * L) {
+    asm volatile("" : "+v"(lane_off));  // (see load_sbase)
+    uint64_t lanes[U][N];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint64_t sb = sgpr_addr(cb + u * NT * L);
+#pragma unroll
+      for (int w = 0; w < N; ++w) lanes[u][w] = load_sbase<uint64_t>(sb, lane_off, w * 8);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      bloom_insert<K>(s_bits, nb, k, BloomFixed<L>(lanes[u]));
+      __builtin_amdgcn_sched_barrier(0);  // one key at a time, as in bloom_keys16_lds
+    }
+  }
+  if (base < n) {  // the tail: under C keys, clamped loads and guarded inserts
     uint64_t lanes[U][N];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -3358,13 +3437,8 @@ enum VqfSlotWord : uint32_t {
 constexpr uint32_t kRingSlotU32 = kSwCount * 64;
 static_assert(kSwCount == 16, "a 4 KiB slot");
 
-// LDS byte addresses (the low word of a generic pointer to LDS is its LDS address)
-typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
+// LDS byte addresses (lds_u32_t, lds_addr: above bloom_insert)
 typedef __attribute__((address_space(3))) uint16_t lds_u16_t;
-__device__ inline uint32_t lds_addr(const void* p)
-{
-  return (uint32_t)reinterpret_cast<uintptr_t>(p);
-}
 __device__ inline uint32_t lds_rd(uint32_t a)
 {
   return *reinterpret_cast<const lds_u32_t*>((uintptr_t)a);
