@@ -52,6 +52,9 @@
  *   tkv_amq_scan_filters    no reference counterpart: a read-only scrub of the filter bytes
  *                           (set bits per Bloom filter, occupied slots and the block invariants
  *                           of vqf_init_in_place / vqf_insert per VQF)
+ *   tkv_amq_verify_members  no reference counterpart: the property the reference's own test pins
+ *                           (tree/in_memory_node.test.cpp:101-131, every key of a leaf passes
+ *                           its filter), audited for a whole batch in one leaf-major pass
  *   tkv_amq_stage_keys      the EditView key range build_filter_for_leaf_in_job iterates
  *                           (core/merge_compactor.hpp:107-139) gathered into one contiguous
  *                           host key buffer for the H2D copy (host only)
@@ -620,6 +623,71 @@ uint64_t tkv_amq_scan_filters_ws_bytes(uint32_t n_segs);
 int tkv_amq_scan_filters(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs,
                          uint32_t n_segs, tkv_amq_filter_stats* d_stats, void* d_workspace,
                          uint64_t workspace_bytes, void* stream);
+
+/* Verify built filters against their keys: does every key of every leaf pass its own filter?
+ * One leaf-major device pass over a batch of filters (plan segments or opened ones) and the
+ * keys they were built from -- the one filter property the reference's tests pin
+ * (tree/in_memory_node.test.cpp:101-131: no false negatives), asked before filter pages are
+ * committed, after a restart has loaded leaf and filter pages, or after an all-gather.
+ * Key i of leaf s is MISSING iff tkv_amq_probe would answer 0 for (key i, segment s); so a VQF
+ * hash dropped by hash_val_shift is present, and a Bloom hash_count other than 7 or 8 takes the
+ * general bit ladder.  keys / key_offsets / key_stride are the key forms of tkv_amq_build (a
+ * fixed stride, or key_offsets[n_keys + 1] on the device), and the 16-byte and 8-byte-aligned
+ * 24-byte fast modes are chosen as the build chooses them (16-byte keys 16-byte aligned).
+ * Which keys belong to leaf s:
+ *  d_key_begin == NULL  keys [seg.key_begin, seg.key_begin + seg.n_keys)
+ *  d_key_begin != NULL  (device, n_segs + 1 entries) keys [d_key_begin[s], d_key_begin[s+1]):
+ *                       the form for opened segments, whose key_begin is 0 and whose VQF n_keys
+ *                       is nelts
+ * Both ends are clamped to n_keys and an end below its begin reads as empty (as
+ * tkv_amq_path_probe treats its lists), so no input causes an out-of-range key read.
+ *  d_result[n_segs]   (device, 16-byte aligned) per leaf: `missing` counts the keys the filter
+ *                     rejects (modulo 2^32), `first_missing` is the smallest global key index
+ *                     among them (~0ull if none), `flags`:
+ *                     NO_FILTER    nothing was checked and missing == 0: a segment the probes
+ *                                  answer 1 for without reading it (the all-zero segment
+ *                                  tkv_amq_open_filters writes for a refused filter, Bloom
+ *                                  hash_count == 0, VQF tag_bits == 0) or one with n_blocks == 0
+ *                     ID_MISMATCH  the 8 bytes the probes' page-id check reads from the payload
+ *                                  (PackedBloomFilterPage @16, PackedVqfFilter @8) differ from
+ *                                  seg.src_page_id.  The keys are still checked: this is an
+ *                                  audit, not reject_page
+ *  d_total_missing    (device, or NULL) the sum of `missing`
+ * The call initialises d_result and d_total_missing itself.  Integer atomics only (atomicAdd,
+ * 64-bit atomicMin), so the output is a function of the input.
+ *  max_seg_blocks     a HINT that sizes the launch's dynamic LDS (the plan's max_seg_blocks; 0 =
+ *                     unknown, or a value past 160 KiB of blocks: the 160 KiB leaf budget).  A
+ *                     leaf whose blocks fit what was allocated is copied into LDS and tested
+ *                     there; any other leaf is tested in global memory by the same kernel.
+ *                     Correctness never depends on the hint
+ *  d_workspace        tkv_amq_verify_members_ws_bytes(n_segs) bytes (host function: >= 16,
+ *                     monotone), 16-byte aligned
+ * The work is split by keys, not by leaf: units of up to chunk_keys consecutive keys of one leaf
+ * (chunk_keys chosen from n_keys alone: about 2,048 units per batch, at least 2,048 keys each),
+ * located through a device-side prefix over the leaves' unit counts in the workspace, one
+ * workgroup per unit; so 6,104 leaves of 16K keys take one workgroup each and one leaf of 3M
+ * keys takes 1,465.
+ * Asynchronous on `stream`, capturable as one linear chain (three kernel launches); no
+ * allocation, no synchronous copy, no synchronisation.  n_segs == 0 is OK (and writes
+ * *d_total_missing = 0 if given).  InvalidArgument, judged before a device is looked for:
+ * unknown kind; with n_segs > 0 a null d_filters, d_segs, d_result or d_workspace, null keys
+ * with n_keys > 0, fixed keys with stride 0, misaligned 16-byte keys, a short or misaligned
+ * workspace; a misaligned d_filters or d_result (16 bytes) or d_total_missing (8).  A valid call
+ * on a machine without a device returns Unavailable. */
+typedef struct tkv_amq_member_check { /* 16 bytes */
+  uint64_t first_missing; /* smallest global key index the filter rejects; ~0ull if none */
+  uint32_t missing;       /* keys of the leaf the filter rejects (false negatives) */
+  uint32_t flags;         /* TKV_AMQ_VERIFY_* */
+} tkv_amq_member_check;
+#define TKV_AMQ_VERIFY_NO_FILTER 0x1u   /* "no filter" segment: nothing was checked */
+#define TKV_AMQ_VERIFY_ID_MISMATCH 0x2u /* payload header src_page_id != the segment's */
+uint64_t tkv_amq_verify_members_ws_bytes(uint32_t n_segs);
+int tkv_amq_verify_members(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs,
+                           uint32_t n_segs, uint32_t max_seg_blocks, const uint8_t* keys,
+                           const uint64_t* key_offsets, uint32_t key_stride, uint64_t n_keys,
+                           const uint64_t* d_key_begin, tkv_amq_member_check* d_result,
+                           uint64_t* d_total_missing, void* d_workspace, uint64_t workspace_bytes,
+                           void* stream);
 
 /* Key staging, host only (no device needed): the H2D front end.  The reference passes the
  * build a flattened range of EditView whose keys are KeyView = std::string_view into leaf /

@@ -303,6 +303,12 @@ class FilterBatchBuilder
                         "tkv_amq_probe");
   }
 
+  // After build_all (same keys, the built d_out): does every leaf's filter hold every key of
+  // the leaf?  Per leaf the tkv_amq_member_check (missing != 0: do not commit that leaf's filter
+  // page).  Synchronises `stream`; defined below verify_members.
+  Status verify(const u8* d_keys, u32 key_stride, const u64* d_key_offsets, const u8* d_out,
+                std::vector<tkv_amq_member_check>& out, hipStream_t stream = nullptr) const;
+
   const std::vector<tkv_amq_segment>& segments() const { return segs_; }
   u64 total_out_bytes() const { return total_out_; }
   const tkv_amq_segment* device_segments() const { return d_segs_.get<tkv_amq_segment>(); }
@@ -403,6 +409,59 @@ inline Status scan_filters(FilterKind kind, const u8* d_filters, const tkv_amq_s
       hipStreamSynchronize(stream) != hipSuccess)
     return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy stats");
   return OkStatus();
+}
+
+// Does every key of every leaf pass its own filter (tkv_amq_verify_members)?  One leaf-major
+// device pass over the filters (plan segments or opened ones) and their keys; per leaf the count
+// of keys the filter rejects -- what tkv_amq_probe would answer 0 for -- the smallest such key
+// index and the TKV_AMQ_VERIFY_* flags.  Leaf s holds keys [d_key_begin[s], d_key_begin[s+1])
+// (device, n_segs + 1 entries: the form for opened segments) or, with d_key_begin == nullptr, the
+// segment's own [key_begin, key_begin + n_keys).  max_seg_blocks: the LDS sizing hint (the
+// plan's, or 0).  total_missing (may be nullptr): the sum.  Synchronises `stream`.
+inline Status verify_members(FilterKind kind, const u8* d_filters, const tkv_amq_segment* d_segs, u32 n_segs,
+                             u32 max_seg_blocks, const u8* d_keys, u32 key_stride, const u64* d_key_offsets,
+                             u64 n_keys, const u64* d_key_begin, std::vector<tkv_amq_member_check>& out,
+                             u64* total_missing = nullptr, hipStream_t stream = nullptr)
+{
+  out.assign(n_segs, tkv_amq_member_check{~u64{0}, 0, 0});
+  if (total_missing) *total_missing = 0;
+  const u64 ws_bytes = tkv_amq_verify_members_ws_bytes(n_segs);
+  if (tkv_amq_device_count() == 0) {
+    // nothing can be allocated: the entry point's own answer (InvalidArgument for a bad call,
+    // else Unavailable); it launches nothing, so aligned host stand-ins serve as its buffers
+    alignas(16) tkv_amq_member_check r{};
+    return Status::from(tkv_amq_verify_members((int)kind, d_filters, d_segs, n_segs, max_seg_blocks, d_keys,
+                                               d_key_offsets, key_stride, n_keys, d_key_begin, &r, nullptr, &r,
+                                               ws_bytes, stream),
+                        "tkv_amq_verify_members");
+  }
+  DeviceBuffer d_result, d_total, d_ws;
+  if (!d_result.resize(sizeof(tkv_amq_member_check) * usize{n_segs}) || !d_total.resize(sizeof(u64)) ||
+      !d_ws.resize(ws_bytes))
+    return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+  const int st = tkv_amq_verify_members((int)kind, d_filters, d_segs, n_segs, max_seg_blocks, d_keys,
+                                        d_key_offsets, key_stride, n_keys, d_key_begin,
+                                        d_result.get<tkv_amq_member_check>(), d_total.get<u64>(), d_ws.get(),
+                                        ws_bytes, stream);
+  if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_verify_members");
+  u64 total = 0;
+  if (hipMemcpyAsync(out.data(), d_result.get(), sizeof(tkv_amq_member_check) * usize{n_segs},
+                     hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipMemcpyAsync(&total, d_total.get(), sizeof(u64), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy member checks");
+  if (total_missing) *total_missing = total;
+  return OkStatus();
+}
+
+inline Status FilterBatchBuilder::verify(const u8* d_keys, u32 key_stride, const u64* d_key_offsets, const u8* d_out,
+                                         std::vector<tkv_amq_member_check>& out, hipStream_t stream) const
+{
+  if (!planned_) return Status::from(TKV_AMQ_INVALID_ARGUMENT, "FilterBatchBuilder::verify before plan()");
+  u64 n = 0;
+  for (u64 c : counts_) n += c;
+  return verify_members(kind_, d_out, d_segs_.get<tkv_amq_segment>(), (u32)segs_.size(), max_blocks_, d_keys,
+                        key_stride, d_key_offsets, n, nullptr, out, nullptr, stream);
 }
 
 // occupied / capacity of one scanned filter: set bits over 512 * n_blocks (Bloom), occupied tag

@@ -14,7 +14,8 @@ from .filters import (BoolStatus, FilterPage, FilterPlan, KeyBatch, KeyQuery, Pa
                       page_header_fields, ProbeMetrics, KeyQueryMetrics, probe_paths,
                       PathProbeResult, path_probe_workspace_bytes, OpenedFilters, open_filters,
                       open_filters_device, scan_filters, scan_filters_device,
-                      scan_filters_workspace_bytes, filter_fill)
+                      scan_filters_workspace_bytes, filter_fill, verify_members,
+                      verify_members_device, verify_members_workspace_bytes)
 
 __all__ = [
     "abi", "BLOOM", "VQF", "TkvAmqError", "BoolStatus", "FilterPage", "FilterPlan", "KeyBatch",
@@ -27,5 +28,6 @@ __all__ = [
     "TreeOptions", "plan_filter_pages", "page_header_fields", "ProbeMetrics", "KeyQueryMetrics",
     "probe_paths", "PathProbeResult", "path_probe_workspace_bytes", "OpenedFilters",
     "open_filters", "open_filters_device", "scan_filters", "scan_filters_device",
-    "scan_filters_workspace_bytes", "filter_fill",
+    "scan_filters_workspace_bytes", "filter_fill", "verify_members", "verify_members_device",
+    "verify_members_workspace_bytes",
 ]

@@ -96,6 +96,7 @@ EXPORTS = [
     "tkv_amq_path_probe_ws_bytes", "tkv_amq_path_probe",
     "tkv_amq_open_filters", "tkv_amq_scan_filters_ws_bytes", "tkv_amq_scan_filters",
     "tkv_amq_build_route",
+    "tkv_amq_verify_members_ws_bytes", "tkv_amq_verify_members",
 ]
 
 # tkv_amq_build_route: TKV_AMQ_ROUTE_* (a Bloom batch's route, or a VQF batch's decide stage),
@@ -128,6 +129,12 @@ FILTER_STATS_DTYPE = np.dtype([
     ("occupied", "<u8"), ("header_items", "<u8"), ("full_blocks", "<u4"), ("empty_blocks", "<u4"),
     ("max_block", "<u4"), ("bad_blocks", "<u4")])
 assert FILTER_STATS_DTYPE.itemsize == 32
+
+# tkv_amq_member_check (16 bytes) and its flags (TKV_AMQ_VERIFY_*)
+MEMBER_CHECK_DTYPE = np.dtype([("first_missing", "<u8"), ("missing", "<u4"), ("flags", "<u4")])
+assert MEMBER_CHECK_DTYPE.itemsize == 16
+VERIFY_NO_FILTER, VERIFY_ID_MISMATCH = 0x1, 0x2
+NONE_MISSING = (1 << 64) - 1  # first_missing of a leaf whose keys all pass
 
 
 class RoutePlan(ctypes.Structure):
@@ -246,6 +253,11 @@ def lib(build_if_missing: bool = True):
         L.tkv_amq_scan_filters_ws_bytes.argtypes = [u32]
         L.tkv_amq_scan_filters.restype = i32
         L.tkv_amq_scan_filters.argtypes = [i32, vp, vp, u32, vp, vp, u64, vp]
+    if hasattr(L, "tkv_amq_verify_members"):
+        L.tkv_amq_verify_members_ws_bytes.restype = u64
+        L.tkv_amq_verify_members_ws_bytes.argtypes = [u32]
+        L.tkv_amq_verify_members.restype = i32
+        L.tkv_amq_verify_members.argtypes = [i32, vp, vp, u32, u32, vp, vp, u32, u64, vp, vp, vp, vp, u64, vp]
     if hasattr(L, "tkv_amq_bloom_route"):
         L.tkv_amq_bloom_route_ws_bytes.restype = u64
         L.tkv_amq_bloom_route_ws_bytes.argtypes = [u64, u32]

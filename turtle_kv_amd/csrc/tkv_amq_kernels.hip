@@ -2585,6 +2585,20 @@ __device__ inline uint32_t probe_block16(const Bloom16& x, uint64_t h0, const ui
   return ok;
 }
 
+// probe_block16's test in pointer form, for a caller that knows its leaf per workgroup and holds
+// the filter's blocks itself (tkv_amq_verify_members): `blk` is the key's 64-byte block as 16
+// words -- W = const lds_u32_t* for an image in LDS (each bit test one ds_read_b32, no staging
+// slot), const uint32_t* for global memory -- and any hasher serves.  The same answer as
+// probe_block16 / bloom_probe_item: the AND of the k bits.  K as in bloom_ladder.
+template <int K, typename H, typename W>
+TKV_INLINE uint32_t bloom_block_test(const H& x, uint64_t h0, W blk, uint32_t k)
+{
+  const uint32_t b0 = (uint32_t)h0;
+  uint32_t ok = blk[(b0 >> 5) & 15u] >> (b0 & 31);
+  bloom_ladder<K>(x, k, [&](uint32_t, uint32_t b) { ok &= blk[(b >> 5) & 15u] >> (b & 31); });
+  return ok & 1u;
+}
+
 // KeyQuery::Metrics tallies of one lane (tkv_amq_probe_ex): per query, the class of its
 // reject_page answer (tree/key_query.hpp:149-247).  Reduced over the wave with shuffles and
 // added to the caller's counters with one atomic per counter per wave.
@@ -4543,27 +4557,51 @@ __global__ __launch_bounds__(kRingThreads) void vqf_ring_place(
 // ---------------------------------------------------------------------------------------
 // VQF probe (PackedVqfFilter::is_present, vqf_filter_page_view.hpp:113-125)
 // ---------------------------------------------------------------------------------------
-template <int T>
+// The block pointer is a type parameter: BP = const uint8_t* reads a filter in global memory (the
+// probes), BP = lds_bytes_t one staged in LDS (tkv_amq_verify_members: its loads are ds_read,
+// not flat).  ld_as<V>(p): the scalar V at p in p's address space; ld_u64x2 / ld_win16: a block's
+// 16 metadata bytes, and a bucket's 16-byte tag window (4-byte aligned: one load from global
+// memory, as the probes always read it; four words from LDS, which the compiler pairs).
+typedef const __attribute__((address_space(3))) uint8_t* lds_bytes_t;
+typedef uint64_t u64x2_t __attribute__((ext_vector_type(2)));
+template <typename V>
+TKV_INLINE V ld_as(const uint8_t* p) { return *reinterpret_cast<const V*>(p); }
+template <typename V>
+TKV_INLINE V ld_as(lds_bytes_t p) { return *reinterpret_cast<const __attribute__((address_space(3))) V*>(p); }
+TKV_INLINE ulonglong2 ld_u64x2(const uint8_t* p) { return *reinterpret_cast<const ulonglong2*>(p); }
+TKV_INLINE ulonglong2 ld_u64x2(lds_bytes_t p)
+{
+  const u64x2_t v = ld_as<u64x2_t>(p);
+  return ulonglong2{v.x, v.y};
+}
+TKV_INLINE uint4 ld_win16(const uint8_t* p) { return *reinterpret_cast<const uint4*>(p); }
+TKV_INLINE uint4 ld_win16(lds_bytes_t p)
+{
+  return uint4{ld_as<uint32_t>(p), ld_as<uint32_t>(p + 4), ld_as<uint32_t>(p + 8), ld_as<uint32_t>(p + 12)};
+}
+
+template <int T, typename BP = const uint8_t*>
 struct VqfBucketRef {
-  const uint8_t* bp;  // the 64-byte block
-  uint32_t o;         // bucket offset inside it
-  uint64_t lo, hi;    // block metadata
+  BP bp;            // the 64-byte block
+  uint32_t o;       // bucket offset inside it
+  uint64_t lo, hi;  // block metadata
 };
 
-template <int T>
-__device__ inline VqfBucketRef<T> vqf_bucket_ref(const uint8_t* blocks, uint32_t idx)
+template <int T, typename BP>
+__device__ inline VqfBucketRef<T, BP> vqf_bucket_ref(BP blocks, uint32_t idx)
 {
   using C = Vqf<T>;
-  VqfBucketRef<T> r;
+  VqfBucketRef<T, BP> r;
   const uint32_t blk = idx / C::kBuckets;
   r.o = idx - blk * C::kBuckets;
-  r.bp = blocks + (uint64_t)blk * 64;
+  if constexpr (std::is_same_v<BP, lds_bytes_t>) r.bp = blocks + (blk << 6);
+  else r.bp = blocks + (uint64_t)blk * 64;
   if constexpr (T == 8) {
-    const ulonglong2 md = *reinterpret_cast<const ulonglong2*>(r.bp);
+    const ulonglong2 md = ld_u64x2(r.bp);
     r.lo = md.x;
     r.hi = md.y;
   } else {
-    r.lo = *reinterpret_cast<const uint64_t*>(r.bp);
+    r.lo = ld_as<uint64_t>(r.bp);
     r.hi = 0;
   }
   return r;
@@ -4582,11 +4620,14 @@ __device__ inline uint32_t zero_halves(uint32_t x)
 // Tags of bucket o are slots [start, end).  One 16-byte load of the tag area starting at the
 // dword that holds slot `start` covers the bucket in almost every case (a bucket holds ~0.6
 // tags on average); longer buckets finish with a per-slot loop.
-template <int T>
-__device__ inline bool vqf_bucket_has(const VqfBucketRef<T>& r, uint32_t tag)
+template <int T, typename BP>
+__device__ inline bool vqf_bucket_has(const VqfBucketRef<T, BP>& r, uint32_t tag)
 {
   using C = Vqf<T>;
   const int o = (int)r.o;
+  // metadata without an (o+1)-th set bit (a damaged block: every block the builds write has
+  // at least kBuckets) holds no bucket o, as the CPU oracle's select reads it: absent
+  if (__popcll(r.lo) + __popcll(r.hi) <= o) return false;
   const int start = o == 0 ? 0 : select128(r.lo, r.hi, o - 1) - (o - 1);
   const int end = select128(r.lo, r.hi, o) - o;
   if (end <= start) return false;
@@ -4594,7 +4635,7 @@ __device__ inline bool vqf_bucket_has(const VqfBucketRef<T>& r, uint32_t tag)
   const int d0 = start / kPer;                          // first dword of the window
   const int last_dword = (C::kSlots * (T / 8)) / 4 - 1; // 11 / 13
   const int d = d0 + 3 <= last_dword ? d0 : last_dword - 3;
-  const uint4 w = *reinterpret_cast<const uint4*>(r.bp + C::kMdBytes + 4 * d);
+  const uint4 w = ld_win16(r.bp + C::kMdBytes + 4 * d);
   const int s0 = start - d * kPer, s1 = end - d * kPer;  // window-relative slot range
   const uint32_t rep = T == 8 ? tag * 0x01010101u : tag * 0x00010001u;
   uint32_t m[4];
@@ -4620,27 +4661,33 @@ __device__ inline bool vqf_bucket_has(const VqfBucketRef<T>& r, uint32_t tag)
   for (int p = d * kPer + kWin; p < end; ++p) {  // rare: bucket runs past the window
     uint32_t tv;
     if constexpr (T == 8) tv = r.bp[C::kMdBytes + p];
-    else tv = *reinterpret_cast<const uint16_t*>(r.bp + C::kMdBytes + 2 * p);
+    else tv = ld_as<uint16_t>(r.bp + C::kMdBytes + 2 * p);
     hit |= tv == tag;
   }
   return hit;
 }
 
-template <int T>
-__device__ inline bool vqf_present(const uint8_t* payload, uint32_t n_blocks, uint64_t magic,
-                                   uint64_t h)
+// is_present over the blocks at `blocks` (global memory or an LDS image, see VqfBucketRef)
+template <int T, typename BP>
+__device__ inline bool vqf_present_at(BP blocks, uint32_t n_blocks, uint64_t magic, uint64_t h)
 {
   using C = Vqf<T>;
   const uint64_t R = (uint64_t)n_blocks * C::kBuckets;
   const uint32_t tag = (uint32_t)(h & ((1ull << T) - 1));
   const uint32_t pi = (uint32_t)mod_by_magic(h >> T, R, magic);
   const uint32_t ai = (uint32_t)mod_by_magic((h ^ ((uint64_t)tag * kVqfAltMul)) >> T, R, magic);
-  const uint8_t* blocks = payload + kVqfHeader + kVqfMetadata;
   // primary bucket first; only the lanes that did not find the tag there read the alternate
   // block (vqf_is_present's order, vqf_filter_page_view.hpp:120-124; loading both blocks up
   // front measured slower)
   if (vqf_bucket_has<T>(vqf_bucket_ref<T>(blocks, pi), tag)) return true;
   return vqf_bucket_has<T>(vqf_bucket_ref<T>(blocks, ai), tag);
+}
+
+template <int T>
+__device__ inline bool vqf_present(const uint8_t* payload, uint32_t n_blocks, uint64_t magic,
+                                   uint64_t h)
+{
+  return vqf_present_at<T>(payload + kVqfHeader + kVqfMetadata, n_blocks, magic, h);
 }
 
 // One VQF (hash, leaf) test: result bit | class << 1.
@@ -7347,3 +7394,6 @@ int tkv_amq_gen_keys16(uint64_t seed, uint64_t first, uint64_t n, uint8_t* d_key
 }
 
 }  // extern "C"
+
+// tkv_amq_verify_members: the leaf-major membership audit
+#include "tkv_amq_verify.h"

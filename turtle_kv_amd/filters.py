@@ -897,6 +897,64 @@ def filter_fill(plan: FilterPlan, stats: np.ndarray) -> np.ndarray:
     occ = stats["occupied"].astype(np.float64)
     return np.divide(occ, cap, out=np.zeros_like(occ), where=cap > 0)
 
+
+# ---------------------------------------------------------------------------------------
+# verify built filters against their keys (no false negatives, per leaf)
+# ---------------------------------------------------------------------------------------
+def verify_members_workspace_bytes(n_segs: int) -> int:
+    """Device workspace tkv_amq_verify_members needs (host only)."""
+    return int(abi.lib().tkv_amq_verify_members_ws_bytes(int(n_segs)))
+
+
+def verify_members_device(kind: int, filters, d_segs, n_segs: int, max_seg_blocks: int, keys, key_offsets,
+                          key_stride: int, n_keys: int, d_key_begin, d_result, d_total, workspace,
+                          stream=None) -> None:
+    """The launches alone (tkv_amq_verify_members), capturable: raw device tensors in, nothing
+    copied back.  d_result: uint8 [16 * n_segs] (MEMBER_CHECK_DTYPE records); d_total: int64 [1]
+    or None; d_key_begin: int64 [n_segs + 1] or None; key_offsets: int64 [n_keys + 1] or None."""
+    _require_device()
+    st = abi.lib().tkv_amq_verify_members(
+        kind, _ptr(filters), _ptr(d_segs), int(n_segs), int(max_seg_blocks), _ptr(keys), _ptr(key_offsets),
+        int(key_stride), int(n_keys), _ptr(d_key_begin), _ptr(d_result), _ptr(d_total), _ptr(workspace),
+        int(workspace.numel()) if workspace is not None else 0, _stream_handle(stream))
+    abi.check(st, "tkv_amq_verify_members")
+
+
+def verify_members(plan_or_opened, filters, keys: KeyBatch, key_begin=None, stream=None,
+                   max_seg_blocks: int | None = None) -> np.ndarray:
+    """Does every key of every leaf pass its own filter?  One leaf-major device pass over the
+    filters of a FilterPlan (or of an OpenedFilters) and the keys they hold: a
+    MEMBER_CHECK_DTYPE record per leaf -- `missing`, the keys the filter rejects (false
+    negatives: what tkv_amq_probe would answer 0 for), `first_missing`, the smallest such key
+    index (abi.NONE_MISSING if none), and `flags` (abi.VERIFY_NO_FILTER: nothing to check;
+    abi.VERIFY_ID_MISMATCH: the payload was built for another page; its keys are checked all the
+    same).  Leaf s holds keys [key_begin[s], key_begin[s+1]) -- n_segs + 1 entries, host or
+    device: the form for opened filters, whose segments do not record their key ranges -- or,
+    without key_begin, the plan's own range.  max_seg_blocks: the LDS sizing hint (the plan's by
+    default); the result never depends on it."""
+    torch = _torch()
+    _require_device()
+    plan = plan_or_opened.plan if isinstance(plan_or_opened, OpenedFilters) else plan_or_opened
+    dev = filters.device
+    n = plan.n_segs
+    d_kb = None
+    if key_begin is not None:
+        d_kb = (key_begin if hasattr(key_begin, "data_ptr") else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(key_begin, dtype=np.uint64)).view(np.int64))).to(
+                device=dev, dtype=torch.int64).contiguous()
+        if int(d_kb.numel()) != n + 1:
+            raise TkvAmqError(abi.INVALID_ARGUMENT, "verify_members: key_begin needs n_segs + 1 entries")
+    d_result = torch.empty(max(n, 1) * 16, dtype=torch.uint8, device=dev)
+    d_total = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(verify_members_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    verify_members_device(plan.kind, filters, plan.device_segs(dev), n,
+                          plan.max_seg_blocks if max_seg_blocks is None else max_seg_blocks, keys.data,
+                          keys.offsets, keys.stride, keys.n, d_kb, d_result, d_total, ws, stream)
+    _hold(stream, d_kb, d_result, d_total, ws)
+    if stream is not None:
+        stream.synchronize()
+    return d_result[:16 * n].cpu().numpy().view(abi.MEMBER_CHECK_DTYPE).copy()
+
 # ---------------------------------------------------------------------------------------
 # single-leaf API (the reference's per-leaf entry points)
 # ---------------------------------------------------------------------------------------
