@@ -486,7 +486,9 @@ int tkv_amq_vqf_probe_hashed_ex(const uint8_t* d_filters, const tkv_amq_segment*
  * computed once and reused for every Bloom filter it is tested against.  Record i lives at
  * d_query + i * tkv_amq_bloom_query_stride(k_max): u64 h0 (block selector and bit 0), then
  * u16 bit index of hash j for j = 1 .. k_max-1.  k_max <= 32; a filter whose hash_count
- * exceeds k_max cannot reject (result 1). */
+ * exceeds k_max cannot be tested with the record, so it cannot reject (result 1).  The _ex
+ * form counts such a pair as no_filter_page_count, like a leaf without a filter, and before
+ * the page-id check: it is never a page_id_mismatch_count. */
 uint32_t tkv_amq_bloom_query_stride(uint32_t k_max);
 int tkv_amq_bloom_hash(const uint8_t* keys, const uint64_t* key_offsets, uint32_t key_stride,
                        uint64_t n_keys, uint32_t k_max, uint8_t* d_query, void* stream);
