@@ -44,6 +44,10 @@
  *                           nodes.hpp:158-187, segmented_levels.hpp:358-369): each key hashed
  *                           once, reject_page asked of every filter on its path, the leaves
  *                           still to search returned per query, in order
+ *   tkv_amq_find_keys       the leaf search behind the filters (find_key_in_leaf_impl, tree/
+ *                           key_query.cpp:27-80,299-327): a lower bound over each surviving
+ *                           leaf's sorted keys, the walk ended at the first leaf that holds the
+ *                           key (tree/algo/nodes.hpp:165-187), filter_false_positive_count (:76-78)
  *   tkv_amq_open_filters    what KeyQuery::reject_page reads from a loaded filter page instead
  *                           of a plan (tree/key_query.hpp:149-247): check_magic()
  *                           (vqf_filter_page_view.hpp:96-100), src_page_id, block_count,
@@ -538,6 +542,92 @@ int tkv_amq_path_probe(int kind, const uint8_t* d_filters, const tkv_amq_segment
                        uint64_t n_entries, uint8_t* d_entry_result, uint32_t* d_cand_begin,
                        uint32_t* d_cand_leaf, uint32_t* d_cand_entry, const tkv_amq_probe_opts* opts,
                        void* d_workspace, uint64_t workspace_bytes, void* stream);
+
+/* Leaf search: resolves a batch of lookups' candidates to found keys (find_key_in_leaf_impl,
+ * tree/key_query.cpp:27-80: std::lower_bound over the leaf's sorted keys and an equality test,
+ * :299-327; the item index reported, :196,327; the walk ended at the first leaf that holds the
+ * key, tree/algo/nodes.hpp:165-187; a false positive counted when a filter that said "maybe"
+ * guarded a leaf without the key, :76-78).  Behind tkv_amq_path_probe it completes a batched
+ * multi-get over device-resident keys: (leaf, item index) per query, and KeyQuery::Metrics
+ * without host truth.
+ * Candidates.  Query i's candidates are positions [d_cand_begin[i], d_cand_begin[i+1]) of
+ * d_cand_leaf, in path order: what tkv_amq_path_probe writes, or any CSR list.  Both ends are
+ * clamped to n_cand and an end below its begin reads as empty.  d_cand_entry is
+ * tkv_amq_path_probe's output of the same name, or NULL.
+ * Leaf keys.  leaf_keys / leaf_key_offsets / leaf_key_stride / n_leaf_keys are the key forms of
+ * tkv_amq_build (leaf_key_offsets[n_leaf_keys + 1] on the device, or a fixed stride).  Leaf s
+ * owns keys [seg.key_begin, seg.key_begin + seg.n_keys), or with d_key_begin (device, n_segs + 1
+ * entries) keys [d_key_begin[s], d_key_begin[s+1]): the form for opened segments, as
+ * tkv_amq_verify_members defines it.  Ranges are clamped to n_leaf_keys.  Query keys and leaf
+ * keys may be of different forms (fixed queries against offset-form leaves, say).
+ * Precondition.  Each leaf's keys are in ascending byte order -- memcmp over the common length,
+ * then the shorter key first: the order of std::string_view.  On an unsorted leaf the result is
+ * whatever the lower-bound procedure yields: defined, never out of range, no membership answer.
+ * Search.  The lower bound of the query key in the leaf's range; FOUND iff that position is
+ * inside the range and the key there equals the query byte for byte and in length.  key_index
+ * is that position as a global index (so the first of a run of equal keys).  An empty leaf is
+ * ABSENT.
+ * Walk.  Candidates are taken in order.  Without TKV_AMQ_FIND_ALL the walk ends at the first
+ * FOUND (the reference: newest level first); later candidates are NOT_SEARCHED and count
+ * nowhere.  With it every candidate is searched; d_result is still the first hit in path order.
+ * False positives.  If opts && opts->d_metrics, a candidate that is searched and ABSENT adds 1
+ * to filter_false_positive_count iff reject_page's class of it is "checked" -- the leaf is in
+ * the plan, its segment has a filter and, when opts->d_query_page_id is given, the filter's
+ * stored page id equals d_query_page_id[d_cand_entry[pos]] -- judged by the code the probes
+ * judge it with.  No other field of tkv_amq_probe_metrics is touched (the path probe has
+ * counted them); opts->d_truth is ignored.  d_filters is read only for the page-id check (8
+ * bytes per such candidate) and may be NULL otherwise; d_cand_entry's values are the caller's
+ * indices into d_query_page_id and are used as given.
+ * Outputs.  d_result[i] is written for every query.  d_cand_state (may be NULL) is written at
+ * every position inside a query's clamped range and nowhere else.  Integer atomics on the
+ * counters only, none on an output position: the output is a function of the input.  (Where
+ * the clamped ranges of a d_cand_begin that is not monotone share positions, d_cand_state there
+ * holds the state one of the covering queries saw; every d_result is still its own query's.)
+ * One lane per query: the workload has about one candidate per query that exists and about none
+ * for one that does not, so the early exit needs no second pass and no atomics; a query with
+ * hundreds of candidates is searched serially by its lane.  16-byte keys (both sides fixed,
+ * 16-byte aligned) and 24-byte keys (both fixed, 8-byte aligned) are compared as big-endian
+ * words; any other shape 8 bytes at a time where both keys have them, then the tail bytes, then
+ * the lengths, never reading past a key's end.
+ * Asynchronous on `stream`: one kernel launch, no workspace, no allocation, no synchronisation;
+ * capturable as a linear chain behind tkv_amq_path_probe.  n_queries == 0 is OK.
+ * InvalidArgument, judged before a device is looked for: unknown kind; unknown flag bits;
+ * n_queries or n_cand above 0xffffffff; a null d_cand_begin, d_result or queries with
+ * n_queries > 0; a null d_cand_leaf with n_cand > 0; a null d_segs with n_segs > 0; null
+ * leaf_keys with n_leaf_keys > 0; a fixed form (no offsets) with stride 0, on either side;
+ * opts->d_query_page_id without d_cand_entry or without d_filters; d_result not 16-byte
+ * aligned; d_counts not 8-byte aligned.  A valid call on a machine without a device returns
+ * Unavailable. */
+typedef struct tkv_amq_find_result { /* 16 bytes */
+  uint64_t key_index; /* global index (into leaf_keys) of the found key; ~0ull if not found */
+  uint32_t leaf;      /* the segment that holds it; 0xffffffff if none */
+  uint32_t cand;      /* position in d_cand_leaf of that candidate; 0xffffffff if none */
+} tkv_amq_find_result;
+
+typedef struct tkv_amq_find_counts { /* 32 bytes, u64 each, ADDED to with atomics (zero to reset) */
+  uint64_t leaf_search_count;  /* candidates searched */
+  uint64_t found_count;        /* queries that found their key */
+  uint64_t absent_count;       /* candidates searched that did not hold the key */
+  uint64_t unsearchable_count; /* candidates naming no leaf of the plan (leaf >= n_segs) */
+} tkv_amq_find_counts;
+
+#define TKV_AMQ_FIND_ALL 0x1u /* search every candidate, not only up to the first hit */
+
+/* per-candidate state, d_cand_state (optional) */
+#define TKV_AMQ_CAND_ABSENT 0u       /* searched, key not in the leaf */
+#define TKV_AMQ_CAND_FOUND 1u        /* searched, key in the leaf */
+#define TKV_AMQ_CAND_NOT_SEARCHED 2u /* the walk had already ended at an earlier candidate */
+#define TKV_AMQ_CAND_UNSEARCHABLE 3u /* leaf >= n_segs */
+
+int tkv_amq_find_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs, uint32_t n_segs,
+                      const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
+                      uint64_t n_queries,
+                      const uint32_t* d_cand_begin, const uint32_t* d_cand_leaf,
+                      const uint32_t* d_cand_entry, uint64_t n_cand,
+                      const uint8_t* leaf_keys, const uint64_t* leaf_key_offsets, uint32_t leaf_key_stride,
+                      uint64_t n_leaf_keys, const uint64_t* d_key_begin,
+                      uint32_t flags, tkv_amq_find_result* d_result, uint8_t* d_cand_state,
+                      const tkv_amq_probe_opts* opts, tkv_amq_find_counts* d_counts, void* stream);
 
 /* Open built filters without a plan (a store restarting on a checkpoint, filter pages received
  * from elsewhere): reconstructs and validates one segment per filter from the filter bytes on

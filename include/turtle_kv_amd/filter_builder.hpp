@@ -1320,6 +1320,56 @@ class KeyQuery
     return OkStatus();
   }
 
+  // The search candidate_leaves leaves to its caller (find_key_in_leaf_impl, key_query.cpp:27-80,
+  // 299-327): key i's candidates cand_leaf[cand_begin[i] .. cand_begin[i+1]) are searched in
+  // order -- a lower bound over the leaf's sorted keys, an equality test -- and the walk ends at
+  // the first leaf that holds the key (tkv_amq_find_keys).
+  //  d_filters, d_segs, segs   as for candidate_leaves
+  //  cand_begin, cand_leaf     candidate_leaves' output (or any CSR list of leaves)
+  //  d_leaf_keys, ...          the leaves' keys on the device, in the key forms of the build
+  //                            (d_leaf_key_offsets != nullptr: variable length); leaf s owns
+  //                            keys [segs[s].key_begin, + segs[s].n_keys), each leaf ascending
+  //  out                       (out) per key: the found key's global index, its leaf and the
+  //                            candidate's position; ~0 / 0xffffffff if no candidate holds it
+  // Adds the device's count of searched candidates that a filter had let through without the
+  // key to metrics().filter_false_positive_count: no host truth is needed.
+  Status find_in_leaves(FilterKind kind, const u8* d_filters, const tkv_amq_segment* d_segs,
+                        const std::vector<tkv_amq_segment>& segs, const std::vector<u32>& cand_begin,
+                        const std::vector<u32>& cand_leaf, const u8* d_leaf_keys, const u64* d_leaf_key_offsets,
+                        u32 leaf_key_stride, u64 n_leaf_keys, std::vector<tkv_amq_find_result>& out)
+  {
+    const u64 n = keys_.size(), n_cand = cand_leaf.size();
+    out.assign(n, tkv_amq_find_result{~u64{0}, ~u32{0}, ~u32{0}});
+    if (tkv_amq_device_count() == 0) return Status::from(TKV_AMQ_UNAVAILABLE, "no HIP device");
+    if (cand_begin.size() != n + 1) return Status::from(TKV_AMQ_INVALID_ARGUMENT, "candidate lists");
+    if (n == 0) return OkStatus();
+    DeviceBuffer d_keys, d_offs, d_begin, d_leaf, d_result, d_metrics;
+    if (!d_begin.resize(4 * (n + 1)) || !d_leaf.resize(4 * n_cand) ||
+        !d_result.resize(sizeof(tkv_amq_find_result) * n) || !d_metrics.resize(sizeof(tkv_amq_probe_metrics)))
+      return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+    bool fixed = false;
+    u32 stride = 16;
+    TKV_AMQ_REQUIRE_OK(detail::stage_keys(keys_, d_keys, d_offs, fixed, stride));
+    if (hipMemcpy(d_begin.get(), cand_begin.data(), 4 * (n + 1), hipMemcpyHostToDevice) != hipSuccess ||
+        (n_cand && hipMemcpy(d_leaf.get(), cand_leaf.data(), 4 * n_cand, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemset(d_metrics.get(), 0, sizeof(tkv_amq_probe_metrics)) != hipSuccess)
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy candidate lists");
+    const tkv_amq_probe_opts opts{nullptr, nullptr, d_metrics.get<tkv_amq_probe_metrics>()};
+    const int st = tkv_amq_find_keys((int)kind, d_filters, d_segs, (u32)segs.size(), d_keys.get(),
+                                     fixed ? nullptr : d_offs.get<u64>(), fixed ? stride : 0, n,
+                                     d_begin.get<u32>(), d_leaf.get<u32>(), nullptr, n_cand, d_leaf_keys,
+                                     d_leaf_key_offsets, leaf_key_stride, n_leaf_keys, nullptr, 0,
+                                     d_result.get<tkv_amq_find_result>(), nullptr, &opts, nullptr, nullptr);
+    if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_find_keys");
+    tkv_amq_probe_metrics pm{};
+    // (blocking copies on the null stream: they wait for the search)
+    if (hipMemcpy(out.data(), d_result.get(), sizeof(tkv_amq_find_result) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&pm, d_metrics.get(), sizeof(pm), hipMemcpyDeviceToHost) != hipSuccess)
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy found keys");
+    metrics().filter_false_positive_count.add(pm.filter_false_positive_count);
+    return OkStatus();
+  }
+
  private:
   std::vector<std::string_view> keys_;
 };

@@ -4,7 +4,7 @@
 // predicated) against one kernel per compile-time length (what a perfectly length-grouped wave
 // would execute).  Compile only, count the v_ instructions of each body:
 //   hipcc --offload-arch=gfx950 -O3 -S --cuda-device-only tools/probe/xxh_short_count.hip \
-//     -Iturtle_kv_amd/csrc -o /tmp/xxh_short.s && python3 tools/probe/count_valu.py /tmp/xxh_short.s
+//     -Iturtle_kv_amd/csrc -Iinclude -o /tmp/xxh_short.s && python3 tools/probe/count_valu.py /tmp/xxh_short.s
 #include <hip/hip_runtime.h>
 
 #include "tkv_amq_device.h"

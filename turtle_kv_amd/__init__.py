@@ -15,7 +15,8 @@ from .filters import (BoolStatus, FilterPage, FilterPlan, KeyBatch, KeyQuery, Pa
                       PathProbeResult, path_probe_workspace_bytes, OpenedFilters, open_filters,
                       open_filters_device, scan_filters, scan_filters_device,
                       scan_filters_workspace_bytes, filter_fill, verify_members,
-                      verify_members_device, verify_members_workspace_bytes)
+                      verify_members_device, verify_members_workspace_bytes, find_keys,
+                      find_keys_device, FindResult, FindCounts)
 
 __all__ = [
     "abi", "BLOOM", "VQF", "TkvAmqError", "BoolStatus", "FilterPage", "FilterPlan", "KeyBatch",
@@ -29,5 +30,5 @@ __all__ = [
     "probe_paths", "PathProbeResult", "path_probe_workspace_bytes", "OpenedFilters",
     "open_filters", "open_filters_device", "scan_filters", "scan_filters_device",
     "scan_filters_workspace_bytes", "filter_fill", "verify_members", "verify_members_device",
-    "verify_members_workspace_bytes",
+    "verify_members_workspace_bytes", "find_keys", "find_keys_device", "FindResult", "FindCounts",
 ]

@@ -97,6 +97,7 @@ EXPORTS = [
     "tkv_amq_open_filters", "tkv_amq_scan_filters_ws_bytes", "tkv_amq_scan_filters",
     "tkv_amq_build_route",
     "tkv_amq_verify_members_ws_bytes", "tkv_amq_verify_members",
+    "tkv_amq_find_keys",
 ]
 
 # tkv_amq_build_route: TKV_AMQ_ROUTE_* (a Bloom batch's route, or a VQF batch's decide stage),
@@ -135,6 +136,18 @@ MEMBER_CHECK_DTYPE = np.dtype([("first_missing", "<u8"), ("missing", "<u4"), ("f
 assert MEMBER_CHECK_DTYPE.itemsize == 16
 VERIFY_NO_FILTER, VERIFY_ID_MISMATCH = 0x1, 0x2
 NONE_MISSING = (1 << 64) - 1  # first_missing of a leaf whose keys all pass
+
+# tkv_amq_find_result (16 bytes), tkv_amq_find_counts (32 bytes), TKV_AMQ_FIND_ALL and the
+# per-candidate states (TKV_AMQ_CAND_*)
+FIND_RESULT_DTYPE = np.dtype([("key_index", "<u8"), ("leaf", "<u4"), ("cand", "<u4")])
+assert FIND_RESULT_DTYPE.itemsize == 16
+FIND_COUNTS_FIELDS = ("leaf_search_count", "found_count", "absent_count", "unsearchable_count")
+FIND_COUNTS_DTYPE = np.dtype([(n, "<u8") for n in FIND_COUNTS_FIELDS])
+assert FIND_COUNTS_DTYPE.itemsize == 32
+FIND_ALL = 0x1
+CAND_ABSENT, CAND_FOUND, CAND_NOT_SEARCHED, CAND_UNSEARCHABLE = range(4)
+NOT_FOUND = (1 << 64) - 1  # key_index of a query whose key no searched candidate holds
+NO_LEAF = 0xFFFFFFFF       # its leaf and cand
 
 
 class RoutePlan(ctypes.Structure):
@@ -258,6 +271,10 @@ def lib(build_if_missing: bool = True):
         L.tkv_amq_verify_members_ws_bytes.argtypes = [u32]
         L.tkv_amq_verify_members.restype = i32
         L.tkv_amq_verify_members.argtypes = [i32, vp, vp, u32, u32, vp, vp, u32, u64, vp, vp, vp, vp, u64, vp]
+    if hasattr(L, "tkv_amq_find_keys"):
+        L.tkv_amq_find_keys.restype = i32
+        L.tkv_amq_find_keys.argtypes = [i32, vp, vp, u32, vp, vp, u32, u64, vp, vp, vp, u64, vp, vp, u32,
+                                        u64, vp, u32, vp, vp, popts, vp, vp]
     if hasattr(L, "tkv_amq_bloom_route"):
         L.tkv_amq_bloom_route_ws_bytes.restype = u64
         L.tkv_amq_bloom_route_ws_bytes.argtypes = [u64, u32]

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tkv_amq.h"
+
 namespace tkv {
 
 constexpr uint64_t kP1 = 0x9E3779B185EBCA87ULL;
@@ -396,6 +398,49 @@ __device__ inline int select128(uint64_t lo, uint64_t hi, int r)
 {
   const int c0 = __popcll(lo);
   return r < c0 ? select64(lo, r) : 64 + select64(hi, r - c0);
+}
+
+__device__ inline uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ---- reject_page's classes, shared by the probes (tkv_amq_kernels.hip) and the leaf search
+// (tkv_amq_find.hip) ----
+// Probe-side view of a segment: the first 16 bytes of tkv_amq_segment in one load.
+struct ProbeDesc {
+  uint64_t out_offset;
+  uint32_t n_blocks;
+  uint32_t hash_count, tag_bits, hash_val_shift;
+};
+
+// A leaf index outside the plan reads as "no filter" (the probe answers "maybe", like
+// reject_page's kUnknown for a page it cannot check, tree/key_query.hpp:156-159): nothing is
+// read out of bounds.
+__device__ inline ProbeDesc load_probe_desc(const tkv_amq_segment* segs, uint32_t s, uint32_t n_segs)
+{
+  const bool in = s < n_segs;
+  const uint4 v = reinterpret_cast<const uint4*>(segs + (in ? s : 0u))[0];
+  ProbeDesc d;
+  d.out_offset = (uint64_t)v.x | ((uint64_t)v.y << 32);
+  d.n_blocks = v.z;
+  d.hash_count = in ? v.w & 0xffffu : 0u;
+  d.tag_bits = in ? (v.w >> 16) & 0xffu : 0u;
+  d.hash_val_shift = v.w >> 24;
+  return d;
+}
+
+enum ProbeClass : uint32_t { kNoFilter = 0, kIdMismatch = 1, kChecked = 2 };
+
+// filter header's src_page_id (PackedBloomFilterPage / PackedVqfFilter) vs the leaf the query
+// asks about (reject_page, tree/key_query.hpp:205-212,227-232): the filter bytes decide, as in
+// the reference
+__device__ inline bool page_id_matches(const uint8_t* payload, uint32_t id_off, const uint64_t* ids,
+                                       uint64_t i)
+{
+  return ids == nullptr || *reinterpret_cast<const uint64_t*>(payload + id_off) == ids[i];
 }
 
 }  // namespace tkv

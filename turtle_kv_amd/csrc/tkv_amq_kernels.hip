@@ -2523,28 +2523,8 @@ __global__ __launch_bounds__(256) void bloom_overflow_multi(const tkv_amq_segmen
 // ---------------------------------------------------------------------------------------
 // Bloom probe
 // ---------------------------------------------------------------------------------------
-// Probe-side view of a segment: the first 16 bytes of tkv_amq_segment in one load.
-struct ProbeDesc {
-  uint64_t out_offset;
-  uint32_t n_blocks;
-  uint32_t hash_count, tag_bits, hash_val_shift;
-};
-
-// A leaf index outside the plan reads as "no filter" (the probe answers "maybe", like
-// reject_page's kUnknown for a page it cannot check, tree/key_query.hpp:156-159): nothing is
-// read out of bounds.
-__device__ inline ProbeDesc load_probe_desc(const tkv_amq_segment* segs, uint32_t s, uint32_t n_segs)
-{
-  const bool in = s < n_segs;
-  const uint4 v = reinterpret_cast<const uint4*>(segs + (in ? s : 0u))[0];
-  ProbeDesc d;
-  d.out_offset = (uint64_t)v.x | ((uint64_t)v.y << 32);
-  d.n_blocks = v.z;
-  d.hash_count = in ? v.w & 0xffffu : 0u;
-  d.tag_bits = in ? (v.w >> 16) & 0xffu : 0u;
-  d.hash_val_shift = v.w >> 24;
-  return d;
-}
+// (ProbeDesc, load_probe_desc, ProbeClass, page_id_matches and wave_sum live in tkv_amq_device.h:
+// tkv_amq_find.hip classifies its candidates with them too)
 
 // One lane per (query, leaf).  The 64-byte filter block is fetched with four 16-byte loads
 // (instead of k divergent 8-byte loads) and staged in a per-lane LDS slot; the k bit tests
@@ -2602,8 +2582,6 @@ TKV_INLINE uint32_t bloom_block_test(const H& x, uint64_t h0, W blk, uint32_t k)
 // KeyQuery::Metrics tallies of one lane (tkv_amq_probe_ex): per query, the class of its
 // reject_page answer (tree/key_query.hpp:149-247).  Reduced over the wave with shuffles and
 // added to the caller's counters with one atomic per counter per wave.
-enum ProbeClass : uint32_t { kNoFilter = 0, kIdMismatch = 1, kChecked = 2 };
-
 struct ProbeTally {
   uint32_t total = 0, no_filter = 0, mismatch = 0, reject = 0, positive = 0, false_pos = 0;
   // r: result bit (1 = maybe present) | class << 1
@@ -2621,13 +2599,6 @@ struct ProbeTally {
   }
 };
 
-__device__ inline uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ inline void flush_tally(const ProbeTally& t, tkv_amq_probe_metrics* m, bool has_truth)
 {
   const uint32_t v[6] = {wave_sum(t.total), wave_sum(t.no_filter), wave_sum(t.mismatch),
@@ -2641,15 +2612,6 @@ __device__ inline void flush_tally(const ProbeTally& t, tkv_amq_probe_metrics* m
     if (v[4]) atomicAdd(&c[4], (unsigned long long)v[4]);
     if (has_truth && v[5]) atomicAdd(&c[5], (unsigned long long)v[5]);
   }
-}
-
-// filter header's src_page_id (PackedBloomFilterPage / PackedVqfFilter) vs the leaf the query
-// asks about (reject_page, tree/key_query.hpp:205-212,227-232): the filter bytes decide, as in
-// the reference
-__device__ inline bool page_id_matches(const uint8_t* payload, uint32_t id_off, const uint64_t* ids,
-                                       uint64_t i)
-{
-  return ids == nullptr || *reinterpret_cast<const uint64_t*>(payload + id_off) == ids[i];
 }
 
 // One Bloom (query, leaf) test: result bit | class << 1 (the class only with kOpts).  Without

@@ -955,6 +955,114 @@ def verify_members(plan_or_opened, filters, keys: KeyBatch, key_begin=None, stre
         stream.synchronize()
     return d_result[:16 * n].cpu().numpy().view(abi.MEMBER_CHECK_DTYPE).copy()
 
+
+# ---------------------------------------------------------------------------------------
+# leaf search: resolve a path probe's candidates to found keys
+# ---------------------------------------------------------------------------------------
+class FindCounts:
+    """Device-side tkv_amq_find_counts that find_keys launches add to; `collect()` reads them."""
+
+    def __init__(self, device=None):
+        torch = _torch()
+        self.counts = torch.zeros(len(abi.FIND_COUNTS_FIELDS), dtype=torch.int64, device=device or "cuda")
+
+    def reset(self) -> None:
+        self.counts.zero_()
+
+    def collect(self) -> dict:
+        return dict(zip(abi.FIND_COUNTS_FIELDS, (int(v) for v in self.counts.cpu().tolist())))
+
+
+@dataclass
+class FindResult:
+    """What find_keys leaves on the device, per query: the global index (into the leaf keys) of
+    the found key (-1, i.e. abi.NOT_FOUND as int64, if none), the leaf that holds it and the
+    position of that candidate in cand_leaf (-1 if none); `state`: one abi.CAND_* byte per
+    candidate position, if asked for.  `raw` is the tkv_amq_find_result array itself (uint8
+    [16 * n_queries], abi.FIND_RESULT_DTYPE records); the three fields are views into it."""
+    key_index: object                    # int64 [n_queries]
+    leaf: object                         # int32 [n_queries]
+    cand: object                         # int32 [n_queries]
+    state: object = None                 # uint8 [n_cand], or None
+    raw: object = field(default=None, repr=False)
+
+
+def find_keys_device(kind: int, filters, d_segs, n_segs: int, queries, query_offsets, query_stride: int,
+                     n_queries: int, cand_begin, cand_leaf, cand_entry, n_cand: int, leaf_keys,
+                     leaf_key_offsets, leaf_key_stride: int, n_leaf_keys: int, d_key_begin, d_result,
+                     d_state=None, flags: int = 0, d_query_page_ids=None, d_metrics=None, d_counts=None,
+                     stream=None) -> None:
+    """The launch alone (tkv_amq_find_keys), capturable behind probe_paths: raw device tensors in,
+    nothing copied back.  cand_begin: int32 [n_queries + 1]; cand_leaf / cand_entry: int32
+    [>= n_cand] (cand_entry may be None); d_result: uint8 [16 * n_queries]
+    (abi.FIND_RESULT_DTYPE records); d_state: uint8 [n_cand] or None; d_key_begin: int64
+    [n_segs + 1] or None; d_query_page_ids: int64 per path ENTRY or None; d_metrics: int64 [6]
+    (ProbeMetrics.counts) or None; d_counts: int64 [4] (FindCounts.counts) or None."""
+    _require_device()
+    o = abi.ProbeOpts(None if d_query_page_ids is None else d_query_page_ids.data_ptr(), None,
+                      None if d_metrics is None else d_metrics.data_ptr())
+    used = d_query_page_ids is not None or d_metrics is not None
+    st = abi.lib().tkv_amq_find_keys(
+        kind, _ptr(filters), _ptr(d_segs), int(n_segs), _ptr(queries), _ptr(query_offsets), int(query_stride),
+        int(n_queries), _ptr(cand_begin), _ptr(cand_leaf), _ptr(cand_entry), int(n_cand), _ptr(leaf_keys),
+        _ptr(leaf_key_offsets), int(leaf_key_stride), int(n_leaf_keys), _ptr(d_key_begin), int(flags),
+        _ptr(d_result), _ptr(d_state), ctypes.byref(o) if used else None, _ptr(d_counts),
+        _stream_handle(stream))
+    abi.check(st, "tkv_amq_find_keys")
+
+
+def find_keys(plan_or_opened, filters, queries: KeyBatch, cands, leaf_keys: KeyBatch, *, key_begin=None,
+              find_all: bool = False, want_state: bool = False, query_page_ids=None,
+              metrics: ProbeMetrics | None = None, counts: FindCounts | None = None,
+              stream=None) -> FindResult:
+    """The leaf search behind the filters (tkv_amq_find_keys): query i's candidates -- a
+    PathProbeResult of probe_paths, or a hand-made (cand_begin, cand_leaf[, cand_entry]) CSR list
+    of segment indices of `plan` -- are searched in path order for queries[i]: a lower bound over
+    the leaf's sorted keys, then an equality test.  The walk ends at the first leaf that holds
+    the key (find_all=True searches every candidate; the result is still the first hit).  Leaf s
+    holds leaf_keys [key_begin[s], key_begin[s+1]) -- n_segs + 1 entries, host or device: the form
+    for opened filters -- or, without key_begin, the plan's own range; each leaf's keys must be in
+    ascending byte order.  With `metrics`, every searched candidate without the key that a filter
+    had let through adds 1 to filter_false_positive_count (query_page_ids: per path ENTRY, as
+    given to probe_paths; needs the candidates' entry indices): together with probe_paths'
+    counts, KeyQuery::Metrics without host truth.  `filters` is read for the page-id check only
+    and may be None otherwise.  Nothing is copied back: the result stays on the device."""
+    torch = _torch()
+    _require_device()
+    plan = plan_or_opened.plan if isinstance(plan_or_opened, OpenedFilters) else plan_or_opened
+    dev = queries.data.device
+    if isinstance(cands, PathProbeResult):
+        cb, cl, ce = cands.cand_begin, cands.cand_leaf, cands.cand_entry
+    else:
+        cb, cl = cands[0], cands[1]
+        ce = cands[2] if len(cands) > 2 else None
+    cb = cb.to(dtype=torch.int32).contiguous()
+    cl = cl.to(dtype=torch.int32).contiguous()
+    ce = None if ce is None else ce.to(dtype=torch.int32).contiguous()
+    if cb.numel() != queries.n + 1:
+        raise ValueError("cand_begin must have one element per query plus one")
+    n_cand = int(cl.numel())
+    n = plan.n_segs
+    d_kb = None
+    if key_begin is not None:
+        d_kb = (key_begin if hasattr(key_begin, "data_ptr") else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(key_begin, dtype=np.uint64)).view(np.int64))).to(
+                device=dev, dtype=torch.int64).contiguous()
+        if int(d_kb.numel()) != n + 1:
+            raise TkvAmqError(abi.INVALID_ARGUMENT, "find_keys: key_begin needs n_segs + 1 entries")
+    pid = None if query_page_ids is None else query_page_ids.to(dtype=torch.int64).contiguous()
+    raw = torch.empty(max(queries.n, 1) * 16, dtype=torch.uint8, device=dev)
+    state = torch.empty(n_cand, dtype=torch.uint8, device=dev) if want_state else None
+    find_keys_device(plan.kind, filters, plan.device_segs(dev) if n else None, n, queries.data,
+                     queries.offsets, queries.stride, queries.n, cb, cl, ce, n_cand, leaf_keys.data,
+                     leaf_keys.offsets, leaf_keys.stride, leaf_keys.n, d_kb, raw, state,
+                     abi.FIND_ALL if find_all else 0, pid, None if metrics is None else metrics.counts,
+                     None if counts is None else counts.counts, stream)
+    _hold(stream, cb, cl, ce, d_kb, pid, raw, state)
+    rec = raw[:16 * queries.n].view(torch.int64).view(queries.n, 2)
+    lc = raw[:16 * queries.n].view(torch.int32).view(queries.n, 4)
+    return FindResult(rec[:, 0], lc[:, 2], lc[:, 3], state, raw)
+
 # ---------------------------------------------------------------------------------------
 # single-leaf API (the reference's per-leaf entry points)
 # ---------------------------------------------------------------------------------------
