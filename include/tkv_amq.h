@@ -48,6 +48,11 @@
  *                           key_query.cpp:27-80,299-327): a lower bound over each surviving
  *                           leaf's sorted keys, the walk ended at the first leaf that holds the
  *                           key (tree/algo/nodes.hpp:165-187), filter_false_positive_count (:76-78)
+ *   tkv_amq_walk_paths      the tree descent in front of both (find_pivot_containing, tree/algo/
+ *                           nodes.hpp:48-71; find_key, :158-187; for_each_active_segment_in,
+ *                           tree/algo/segmented_levels.hpp:340-369): each lookup's ordered list of
+ *                           leaves, with page ids, flushed item upper bounds (packed_node_page.cpp:
+ *                           231-248) and (depth, level) per entry
  *   tkv_amq_open_filters    what KeyQuery::reject_page reads from a loaded filter page instead
  *                           of a plan (tree/key_query.hpp:149-247): check_magic()
  *                           (vqf_filter_page_view.hpp:96-100), src_page_id, block_count,
@@ -628,6 +633,109 @@ int tkv_amq_find_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment*
                       uint64_t n_leaf_keys, const uint64_t* d_key_begin,
                       uint32_t flags, tkv_amq_find_result* d_result, uint8_t* d_cand_state,
                       const tkv_amq_probe_opts* opts, tkv_amq_find_counts* d_counts, void* stream);
+
+/* Tree walk: resolves a batch of lookups to the paths tkv_amq_path_probe and tkv_amq_find_keys
+ * start from (find_pivot_containing, tree/algo/nodes.hpp:48-71; find_key, :158-187;
+ * for_each_active_segment_in / find_key, tree/algo/segmented_levels.hpp:340-369; the shapes of
+ * PackedNodePage, tree/packed_node_page.hpp:42-223; get_flushed_item_upper_bound,
+ * packed_node_page.cpp:231-248).  Keys -> paths -> candidates -> found keys is then three calls on
+ * one stream with no host work between them.
+ * The tree is flat, caller-owned device memory; node 0 is the root.
+ *  nodes[n_nodes]             a node owns pivot_count + 1 keys k0..kp of the pivot-key list from
+ *                             pivot_key_begin, the segments of its update buffer from seg_begin
+ *                             (level l: [seg_begin + level_start[l], seg_begin + level_start[l+1]),
+ *                             as UpdateBuffer::level_start) and one child per pivot from child_begin
+ *  segments[n_segments]       one update-buffer segment: the leaf it names, in the filter plan
+ *                             (`leaf`, passed through as given: 0xffffffff or any leaf >= the probe's
+ *                             n_segs is "cannot reject" there) and as a page id; active_pivots and
+ *                             flushed_pivots, one bit per pivot
+ *  children[n_children]       page id and index: a node index under a parent of height > 1, a leaf
+ *                             index (as `leaf` above) under one of height 1 (or 0, read as 1)
+ *  d_flushed_bounds[n_flushed_bounds]  u32; a segment's bound for pivot p is 0 if bit p of
+ *                             flushed_pivots is clear, else d_flushed_bounds[flushed_begin + the
+ *                             number of set bits of flushed_pivots below p] (bit_rank)
+ *  pivot_keys / pivot_key_offsets / pivot_key_stride / n_pivot_keys   the key forms of
+ *                             tkv_amq_build; queries likewise
+ * Per query, from node 0 at depth 0:
+ *  1. p = the number of the node's interior keys k1..k(pivot_count-1) that are <= the query: an
+ *     upper_bound in std::string_view order (tkv_amq_find_keys' order).  k0 and kp are never read;
+ *     pivot_count == 1 gives p = 0 and reads no key.
+ *  2. for level 0 .. level_count-1, for each segment of the level in order: if bit p of its
+ *     active_pivots is set, the entry (leaf, leaf_page_id, flushed bound for p, depth << 8 | level)
+ *  3. child p: under height <= 1 the entry (index, page_id, 0, depth << 8 | 0xff) and the walk ends;
+ *     otherwise the walk goes on in node `index` at depth + 1.
+ * Output: a CSR list in that order.  d_path_begin[i] is the exact prefix sum clamped to
+ * path_capacity (d_path_begin[n_queries] = min(total, path_capacity)); entries at positions below
+ * path_capacity are written to d_path_leaf and to each of d_path_page_id / d_path_flushed /
+ * d_path_where that is given; nothing is written at or past path_capacity; *d_needed (if given)
+ * is the unclamped total, so a caller sees a short capacity and can retry.  The output is a
+ * function of the input: no atomics.  d_path_flushed and d_path_where are for a search that knows
+ * the reference's rule "found below the flushed bound: skip the rest of the level"
+ * (tree/algo/segments.hpp:185-200); tkv_amq_find_keys does not read them yet.
+ * Malformed trees get a defined answer and never an out-of-range read:
+ *  - interior keys at or past n_pivot_keys do not exist (the search runs over those that do)
+ *  - a level's segment range is clamped to n_segments; level_start[l+1] < level_start[l] reads as
+ *    an empty level; level_count above 7 reads as 7
+ *  - a flushed-bound index at or past n_flushed_bounds reads as 0
+ *  - the walk ends, with what it has emitted, at a node index >= n_nodes (n_nodes == 0: every path
+ *    is empty), at pivot_count 0 or > 64, at a child slot >= n_children, and after
+ *    TKV_AMQ_WALK_MAX_DEPTH nodes (so a cycle terminates)
+ * Chaining without a host read: give tkv_amq_path_probe n_entries = path_capacity and a workspace
+ * sized for it (its paths then lie below the total), and d_path_page_id as opts->d_query_page_id.
+ * Asynchronous on `stream`: three kernel launches (count, scan, write; an empty batch: one), no
+ * allocation, no synchronisation; capturable as a linear chain in front of tkv_amq_path_probe.
+ * n_queries == 0 is OK and writes d_path_begin[0] = 0 and *d_needed = 0 (each if given).
+ *  d_workspace   tkv_amq_walk_paths_ws_bytes(n_queries) bytes (host function: >= 16, monotone, 0
+ *                for counts the walk refuses), 16-byte aligned: 16 bytes per query (its pivot at
+ *                each depth, 6 bits x 16) and 8 per 256 queries
+ * InvalidArgument, judged before a device is looked for: any count above 0xffffffff; a null
+ * nodes / segments / children / d_flushed_bounds / pivot_keys / queries with its count non-zero; a
+ * null d_path_begin or d_workspace with n_queries > 0; a null d_path_leaf with path_capacity > 0;
+ * a fixed key form (no offsets) with stride 0, on either side; nodes, segments or children not
+ * 16-byte aligned; d_needed not 8-byte aligned; a short or misaligned workspace.  A valid call on
+ * a machine without a device returns Unavailable. */
+#define TKV_AMQ_WALK_MAX_DEPTH 16u
+#define TKV_AMQ_WALK_LEAF_LEVEL 0xffu /* d_path_where's level byte of a child-leaf entry */
+
+typedef struct tkv_amq_tree_node { /* 32 bytes */
+  uint32_t pivot_key_begin; /* index of k0 in the pivot-key list */
+  uint32_t seg_begin;       /* index of the node's first segment */
+  uint32_t child_begin;     /* child of pivot i is children[child_begin + i] */
+  uint32_t reserved0;
+  uint8_t pivot_count;      /* 1..64 */
+  uint8_t height;           /* 1: the children are leaves */
+  uint8_t level_count;      /* 0..7 */
+  uint8_t reserved1;
+  uint8_t level_start[8];   /* level l: segments [level_start[l], level_start[l+1]) from seg_begin */
+  uint32_t reserved2;
+} tkv_amq_tree_node;
+
+typedef struct tkv_amq_tree_segment { /* 32 bytes */
+  uint64_t leaf_page_id;    /* the leaf's page id */
+  uint64_t active_pivots;   /* bit p: the segment holds items of pivot p */
+  uint64_t flushed_pivots;  /* bit p: pivot p has a flushed item upper bound */
+  uint32_t leaf;            /* the leaf's segment index in the filter plan */
+  uint32_t flushed_begin;   /* index of the segment's first bound in d_flushed_bounds */
+} tkv_amq_tree_segment;
+
+typedef struct tkv_amq_tree_child { /* 16 bytes */
+  uint64_t page_id;         /* the child's page id */
+  uint32_t index;           /* node index (parent height > 1) or leaf index (height 1) */
+  uint32_t reserved;
+} tkv_amq_tree_child;
+
+uint64_t tkv_amq_walk_paths_ws_bytes(uint64_t n_queries);
+int tkv_amq_walk_paths(const tkv_amq_tree_node* nodes, uint64_t n_nodes,
+                       const tkv_amq_tree_segment* segments, uint64_t n_segments,
+                       const tkv_amq_tree_child* children, uint64_t n_children,
+                       const uint32_t* d_flushed_bounds, uint64_t n_flushed_bounds,
+                       const uint8_t* pivot_keys, const uint64_t* pivot_key_offsets,
+                       uint32_t pivot_key_stride, uint64_t n_pivot_keys,
+                       const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
+                       uint64_t n_queries, uint32_t* d_path_begin, uint32_t* d_path_leaf,
+                       uint64_t* d_path_page_id, uint32_t* d_path_flushed, uint16_t* d_path_where,
+                       uint64_t path_capacity, uint64_t* d_needed, void* d_workspace,
+                       uint64_t workspace_bytes, void* stream);
 
 /* Open built filters without a plan (a store restarting on a checkpoint, filter pages received
  * from elsewhere): reconstructs and validates one segment per filter from the filter bytes on

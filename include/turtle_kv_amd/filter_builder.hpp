@@ -18,6 +18,8 @@
 //                                                                          FilterBatchBuilder::plan_pages
 //   reject_page's read of a loaded page   tree/key_query.hpp:149-247, vqf_filter_page_view.hpp:96-100
 //                                                                          open_filter_pages, scan_filters
+//   find_pivot_containing / find_key      tree/algo/nodes.hpp:48-71,158-187, tree/algo/segmented_levels.hpp:340-369
+//                                                                          TreeIndex, KeyQuery::walk_paths
 //
 // The single-leaf functions take the leaf's keys as host string views (the reference's
 // `items` range of EditView keys, tombstones included) and fill a host page payload
@@ -28,6 +30,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -39,6 +42,7 @@
 #include <string>
 #include <string_view>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../tkv_amq.h"
@@ -1127,6 +1131,284 @@ inline Status build_filter_for_leaf_in_job_batched(usize filter_bits_per_key, u6
 enum class BoolStatus : int { kFalse = 0, kTrue = 1, kUnknown = 2 };
 
 // FastCountMetric<u64>
+// ---------------------------------------------------------------------------------------
+// TreeIndex: the flat tree tkv_amq_walk_paths descends (find_pivot_containing, tree/algo/
+// nodes.hpp:48-71; find_key, :158-187; for_each_active_segment_in, tree/algo/
+// segmented_levels.hpp:340-369; the shapes of PackedNodePage, tree/packed_node_page.hpp:42-223)
+// ---------------------------------------------------------------------------------------
+// The CSR list a walk produces: key i's entries are [begin[i], begin[i+1]) of every array.
+struct TreePaths {
+  std::vector<u32> begin, leaf, flushed;
+  std::vector<u64> page_id;
+  std::vector<u16> where;  // depth << 8 | level; level TKV_AMQ_WALK_LEAF_LEVEL: the child leaf
+
+  void clear(usize n_keys)
+  {
+    begin.assign(n_keys + 1, 0);
+    leaf.clear();
+    flushed.clear();
+    page_id.clear();
+    where.clear();
+  }
+};
+
+class TreeIndex
+{
+ public:
+  static constexpr usize kMaxPivots = 64, kMaxSegments = 63, kMaxLevels = 7;  // (the reference's page: 6 levels)
+
+  struct Segment {
+    u32 leaf = 0;            // the leaf's segment index in the filter plan
+    u64 page_id = 0;
+    u64 active_pivots = 0;
+    std::vector<std::pair<u32, u32>> flushed;  // (pivot, flushed item upper bound)
+  };
+  struct Leaf {
+    u32 leaf = 0;
+    u64 page_id = 0;
+  };
+  // A node owns pivot_count + 1 keys and one child per pivot: `children` (nodes) or `leaves`,
+  // never both.  levels: the update buffer, newest first.
+  struct Node {
+    std::vector<std::string> pivot_keys;
+    std::vector<std::vector<Segment>> levels;
+    std::vector<Node> children;
+    std::vector<Leaf> leaves;
+    u64 page_id = 0;
+  };
+
+  // Validates the PackedNodePage limits and flattens the description breadth first (node 0 is
+  // the root).
+  static Status build(const Node& root, TreeIndex& out)
+  {
+    out.reset();
+    int height = 0;
+    TKV_AMQ_REQUIRE_OK(validate(root, height));
+    if (height > (int)TKV_AMQ_WALK_MAX_DEPTH) return Status::from(TKV_AMQ_INVALID_ARGUMENT, "tree height");
+    std::vector<std::pair<const Node*, int>> order{{&root, height}};
+    for (usize at = 0; at < order.size(); ++at)
+      for (const Node& c : order[at].first->children) order.push_back({&c, order[at].second - 1});
+    usize next_child_node = 1;
+    for (const auto& [n, h] : order) {
+      tkv_amq_tree_node f{};
+      const usize pivots = n->children.empty() ? n->leaves.size() : n->children.size();
+      f.pivot_key_begin = (u32)out.pivot_keys_.size();
+      f.seg_begin = (u32)out.segments_.size();
+      f.child_begin = (u32)out.children_.size();
+      f.pivot_count = (u8)pivots;
+      f.height = (u8)h;
+      f.level_count = (u8)n->levels.size();
+      usize start = 0;
+      for (usize l = 0; l < 8; ++l) {
+        f.level_start[l] = (u8)start;
+        if (l < n->levels.size()) start += n->levels[l].size();
+      }
+      for (const auto& k : n->pivot_keys) out.pivot_keys_.push_back(k);
+      for (const Node& c : n->children) out.children_.push_back(tkv_amq_tree_child{c.page_id, (u32)next_child_node++, 0});
+      for (const Leaf& c : n->leaves) out.children_.push_back(tkv_amq_tree_child{c.page_id, c.leaf, 0});
+      for (const auto& level : n->levels) {
+        for (const Segment& s : level) {
+          tkv_amq_tree_segment g{};
+          g.leaf_page_id = s.page_id;
+          g.active_pivots = s.active_pivots;
+          g.leaf = s.leaf;
+          g.flushed_begin = (u32)out.flushed_bounds_.size();
+          auto fl = s.flushed;
+          std::sort(fl.begin(), fl.end());  // bounds are stored in pivot order (bit_rank)
+          for (const auto& [p, bound] : fl) {
+            g.flushed_pivots |= u64{1} << p;
+            out.flushed_bounds_.push_back(bound);
+          }
+          out.segments_.push_back(g);
+        }
+      }
+      out.nodes_.push_back(f);
+    }
+    return OkStatus();
+  }
+
+  // A tree that is flat already (read back from a file, say).  Nothing is validated: the walks
+  // clamp every index.
+  static void from_flat(std::vector<tkv_amq_tree_node> nodes, std::vector<tkv_amq_tree_segment> segments,
+                        std::vector<tkv_amq_tree_child> children, std::vector<u32> flushed_bounds,
+                        std::vector<std::string> pivot_keys, TreeIndex& out)
+  {
+    out.reset();
+    out.nodes_ = std::move(nodes);
+    out.segments_ = std::move(segments);
+    out.children_ = std::move(children);
+    out.flushed_bounds_ = std::move(flushed_bounds);
+    out.pivot_keys_ = std::move(pivot_keys);
+  }
+
+  const std::vector<tkv_amq_tree_node>& nodes() const { return nodes_; }
+  const std::vector<tkv_amq_tree_segment>& segments() const { return segments_; }
+  const std::vector<tkv_amq_tree_child>& children() const { return children_; }
+  const std::vector<u32>& flushed_bounds() const { return flushed_bounds_; }
+  const std::vector<std::string>& pivot_keys() const { return pivot_keys_; }
+
+  // The same walk on the host, written with std::upper_bound: the comparator of the tests and
+  // the CPU baseline.  It applies the clamps of tkv_amq_walk_paths, so it answers for any flat
+  // tree.  n_threads > 1 splits the keys into contiguous ranges.
+  void walk_host(const std::vector<std::string_view>& keys, TreePaths& out, unsigned n_threads = 1) const
+  {
+    const usize n = keys.size();
+    out.clear(n);
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > n) n_threads = n ? (unsigned)n : 1;
+    std::vector<std::string_view> pk(pivot_keys_.begin(), pivot_keys_.end());
+    std::vector<TreePaths> part(n_threads);
+    std::vector<std::thread> pool;
+    auto work = [&](unsigned t) {
+      const usize b = n * t / n_threads, e = n * (t + 1) / n_threads;
+      TreePaths& o = part[t];
+      o.begin.assign(e - b + 1, 0);
+      for (usize i = b; i < e; ++i) {
+        walk_one(pk, keys[i], o);
+        o.begin[i - b + 1] = (u32)o.leaf.size();
+      }
+    };
+    for (unsigned t = 1; t < n_threads; ++t) pool.emplace_back(work, t);
+    work(0);
+    for (auto& th : pool) th.join();
+    for (unsigned t = 0; t < n_threads; ++t) {
+      const usize b = n * t / n_threads, base = out.leaf.size();
+      const TreePaths& o = part[t];
+      for (usize j = 1; j < o.begin.size(); ++j) out.begin[b + j] = (u32)(base + o.begin[j]);
+      out.leaf.insert(out.leaf.end(), o.leaf.begin(), o.leaf.end());
+      out.flushed.insert(out.flushed.end(), o.flushed.begin(), o.flushed.end());
+      out.page_id.insert(out.page_id.end(), o.page_id.begin(), o.page_id.end());
+      out.where.insert(out.where.end(), o.where.begin(), o.where.end());
+    }
+  }
+
+  // The flat arrays on the device, uploaded once (pivot keys fixed-stride if they share a length).
+  Status upload()
+  {
+    if (uploaded_) return OkStatus();
+    if (tkv_amq_device_count() == 0) return Status::from(TKV_AMQ_UNAVAILABLE, "no HIP device");
+    std::vector<std::string_view> pk(pivot_keys_.begin(), pivot_keys_.end());
+    TKV_AMQ_REQUIRE_OK(detail::stage_keys(pk, d_keys_, d_key_offs_, keys_fixed_, key_stride_));
+    auto put = [](DeviceBuffer& d, const void* p, usize bytes) {
+      return d.resize(bytes) && (bytes == 0 || hipMemcpy(d.get(), p, bytes, hipMemcpyHostToDevice) == hipSuccess);
+    };
+    if (!put(d_nodes_, nodes_.data(), nodes_.size() * sizeof(tkv_amq_tree_node)) ||
+        !put(d_segments_, segments_.data(), segments_.size() * sizeof(tkv_amq_tree_segment)) ||
+        !put(d_children_, children_.data(), children_.size() * sizeof(tkv_amq_tree_child)) ||
+        !put(d_bounds_, flushed_bounds_.data(), flushed_bounds_.size() * 4))
+      return Status::from(TKV_AMQ_INTERNAL, "tree upload");
+    uploaded_ = true;
+    return OkStatus();
+  }
+
+  // tkv_amq_walk_paths over the uploaded tree (upload() first); every pointer is a device pointer
+  int walk_device(const u8* d_queries, const u64* d_query_offsets, u32 query_stride, u64 n_queries,
+                  u32* d_path_begin, u32* d_path_leaf, u64* d_path_page_id, u32* d_path_flushed, u16* d_path_where,
+                  u64 path_capacity, u64* d_needed, void* d_workspace, u64 workspace_bytes,
+                  hipStream_t stream = nullptr) const
+  {
+    return tkv_amq_walk_paths(d_nodes_.get<tkv_amq_tree_node>(), nodes_.size(),
+                              d_segments_.get<tkv_amq_tree_segment>(), segments_.size(),
+                              d_children_.get<tkv_amq_tree_child>(), children_.size(), d_bounds_.get<u32>(),
+                              flushed_bounds_.size(), d_keys_.get(), keys_fixed_ ? nullptr : d_key_offs_.get<u64>(),
+                              keys_fixed_ ? key_stride_ : 0, pivot_keys_.size(), d_queries, d_query_offsets,
+                              query_stride, n_queries, d_path_begin, d_path_leaf, d_path_page_id, d_path_flushed,
+                              d_path_where, path_capacity, d_needed, d_workspace, workspace_bytes, stream);
+  }
+
+ private:
+  static Status validate(const Node& n, int& height)
+  {
+    const auto bad = [](const char* w) { return Status::from(TKV_AMQ_INVALID_ARGUMENT, w); };
+    if (!n.children.empty() && !n.leaves.empty()) return bad("a node's children are all nodes or all leaves");
+    const usize pivots = n.children.empty() ? n.leaves.size() : n.children.size();
+    if (pivots < 1 || pivots > kMaxPivots) return bad("a node has 1..64 pivots");
+    if (n.pivot_keys.size() != pivots + 1) return bad("a node of p pivots owns p + 1 pivot keys");
+    if (n.levels.size() > kMaxLevels) return bad("a node has at most 7 levels");
+    usize n_seg = 0;
+    for (const auto& level : n.levels) {
+      n_seg += level.size();
+      for (const Segment& s : level) {
+        if (pivots < 64 && (s.active_pivots >> pivots)) return bad("a segment names a pivot the node does not have");
+        for (const auto& f : s.flushed)
+          if (f.first >= pivots) return bad("a segment names a pivot the node does not have");
+      }
+    }
+    if (n_seg > kMaxSegments) return bad("a node has at most 63 segments");
+    height = 1;
+    for (usize i = 0; i < n.children.size(); ++i) {
+      int h = 0;
+      TKV_AMQ_REQUIRE_OK(validate(n.children[i], h));
+      if (i && h + 1 != height) return bad("a node's children have one height");
+      height = h + 1;
+    }
+    return OkStatus();
+  }
+
+  void walk_one(const std::vector<std::string_view>& pk, std::string_view q, TreePaths& o) const
+  {
+    u32 ni = 0;
+    for (u32 depth = 0; depth < TKV_AMQ_WALK_MAX_DEPTH; ++depth) {
+      if (ni >= nodes_.size()) return;
+      const tkv_amq_tree_node& nd = nodes_[ni];
+      if (nd.pivot_count == 0 || nd.pivot_count > 64) return;
+      // the interior keys k1..k(p-1); those past the list do not exist
+      const usize first = std::min<usize>((usize)nd.pivot_key_begin + 1, pk.size());
+      const usize last = std::min<usize>(first + nd.pivot_count - 1, pk.size());
+      const u32 p = (u32)(std::upper_bound(pk.begin() + first, pk.begin() + last, q) - (pk.begin() + first));
+      const usize levels = std::min<usize>(nd.level_count, 7);
+      for (usize l = 0; l < levels; ++l) {
+        const usize sb = std::min<usize>((usize)nd.seg_begin + nd.level_start[l], segments_.size());
+        const usize se = std::min<usize>((usize)nd.seg_begin + nd.level_start[l + 1], segments_.size());
+        for (usize s = sb; s < se; ++s) {
+          const tkv_amq_tree_segment& g = segments_[s];
+          if (!((g.active_pivots >> p) & 1)) continue;
+          u32 bound = 0;
+          if ((g.flushed_pivots >> p) & 1) {
+            const usize at = (usize)g.flushed_begin + (usize)__builtin_popcountll(g.flushed_pivots & ((u64{1} << p) - 1));
+            if (at < flushed_bounds_.size()) bound = flushed_bounds_[at];
+          }
+          push(o, g.leaf, g.leaf_page_id, bound, (u16)(depth << 8 | l));
+        }
+      }
+      const usize c = (usize)nd.child_begin + p;
+      if (c >= children_.size()) return;
+      if (nd.height <= 1) {
+        push(o, children_[c].index, children_[c].page_id, 0, (u16)(depth << 8 | TKV_AMQ_WALK_LEAF_LEVEL));
+        return;
+      }
+      ni = children_[c].index;
+    }
+  }
+
+  void reset()
+  {
+    nodes_.clear();
+    segments_.clear();
+    children_.clear();
+    flushed_bounds_.clear();
+    pivot_keys_.clear();
+    uploaded_ = false;
+  }
+
+  static void push(TreePaths& o, u32 leaf, u64 page_id, u32 flushed, u16 where)
+  {
+    o.leaf.push_back(leaf);
+    o.page_id.push_back(page_id);
+    o.flushed.push_back(flushed);
+    o.where.push_back(where);
+  }
+
+  std::vector<tkv_amq_tree_node> nodes_;
+  std::vector<tkv_amq_tree_segment> segments_;
+  std::vector<tkv_amq_tree_child> children_;
+  std::vector<u32> flushed_bounds_;
+  std::vector<std::string> pivot_keys_;
+  DeviceBuffer d_nodes_, d_segments_, d_children_, d_bounds_, d_keys_, d_key_offs_;
+  bool uploaded_ = false, keys_fixed_ = false;
+  u32 key_stride_ = 0;
+};
+
 struct CountMetric {
   std::atomic<u64> value{0};
   void add(u64 n) { value.fetch_add(n, std::memory_order_relaxed); }
@@ -1317,6 +1599,55 @@ class KeyQuery
     m.filter_reject_count.add(pm.filter_reject_count);
     m.filter_positive_count.add(pm.filter_positive_count);
     if (truth) m.filter_false_positive_count.add(pm.filter_false_positive_count);
+    return OkStatus();
+  }
+
+  // The descent in front of candidate_leaves (tkv_amq_walk_paths): every key's ordered list of
+  // leaves over `tree`, with page ids, flushed item upper bounds and (depth, level) per entry --
+  // what TreeIndex::walk_host computes on the host.  out.begin / out.leaf are candidate_leaves'
+  // path_begin / path_leaf.  Synchronises: the walk runs once with capacity 0 to learn the total,
+  // then again with exactly that capacity.
+  Status walk_paths(TreeIndex& tree, TreePaths& out)
+  {
+    const u64 n = keys_.size();
+    out.clear(n);
+    if (tkv_amq_device_count() == 0) return Status::from(TKV_AMQ_UNAVAILABLE, "no HIP device");
+    if (n == 0) return OkStatus();
+    TKV_AMQ_REQUIRE_OK(tree.upload());
+    const u64 ws_bytes = tkv_amq_walk_paths_ws_bytes(n);
+    if (ws_bytes == 0) return Status::from(TKV_AMQ_INVALID_ARGUMENT, "too many keys");
+    DeviceBuffer d_keys, d_offs, d_begin, d_needed, d_ws, d_leaf, d_page, d_flushed, d_where;
+    if (!d_begin.resize(4 * (n + 1)) || !d_needed.resize(8) || !d_ws.resize(ws_bytes))
+      return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+    bool fixed = false;
+    u32 stride = 16;
+    TKV_AMQ_REQUIRE_OK(detail::stage_keys(keys_, d_keys, d_offs, fixed, stride));
+    const u64* offs = fixed ? nullptr : d_offs.get<u64>();
+    int st = tree.walk_device(d_keys.get(), offs, fixed ? stride : 0, n, d_begin.get<u32>(), nullptr, nullptr,
+                              nullptr, nullptr, 0, d_needed.get<u64>(), d_ws.get(), ws_bytes);
+    if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_walk_paths");
+    u64 total = 0;
+    // (blocking copies on the null stream: they wait for the walk)
+    if (hipMemcpy(&total, d_needed.get(), 8, hipMemcpyDeviceToHost) != hipSuccess)
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy total");
+    if (total > 0xffffffffull) return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "more than 2^32 entries");
+    if (!d_leaf.resize(4 * total) || !d_page.resize(8 * total) || !d_flushed.resize(4 * total) ||
+        !d_where.resize(2 * total))
+      return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+    st = tree.walk_device(d_keys.get(), offs, fixed ? stride : 0, n, d_begin.get<u32>(), d_leaf.get<u32>(),
+                          d_page.get<u64>(), d_flushed.get<u32>(), d_where.get<u16>(), total, d_needed.get<u64>(),
+                          d_ws.get(), ws_bytes);
+    if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_walk_paths");
+    out.leaf.resize(total);
+    out.page_id.resize(total);
+    out.flushed.resize(total);
+    out.where.resize(total);
+    if (hipMemcpy(out.begin.data(), d_begin.get(), 4 * (n + 1), hipMemcpyDeviceToHost) != hipSuccess ||
+        (total && (hipMemcpy(out.leaf.data(), d_leaf.get(), 4 * total, hipMemcpyDeviceToHost) != hipSuccess ||
+                   hipMemcpy(out.page_id.data(), d_page.get(), 8 * total, hipMemcpyDeviceToHost) != hipSuccess ||
+                   hipMemcpy(out.flushed.data(), d_flushed.get(), 4 * total, hipMemcpyDeviceToHost) != hipSuccess ||
+                   hipMemcpy(out.where.data(), d_where.get(), 2 * total, hipMemcpyDeviceToHost) != hipSuccess)))
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy paths");
     return OkStatus();
   }
 

@@ -16,7 +16,8 @@ from .filters import (BoolStatus, FilterPage, FilterPlan, KeyBatch, KeyQuery, Pa
                       open_filters_device, scan_filters, scan_filters_device,
                       scan_filters_workspace_bytes, filter_fill, verify_members,
                       verify_members_device, verify_members_workspace_bytes, find_keys,
-                      find_keys_device, FindResult, FindCounts)
+                      find_keys_device, FindResult, FindCounts, TreeIndex, WalkResult, walk_paths,
+                      walk_paths_device, walk_paths_workspace_bytes)
 
 __all__ = [
     "abi", "BLOOM", "VQF", "TkvAmqError", "BoolStatus", "FilterPage", "FilterPlan", "KeyBatch",
@@ -31,4 +32,5 @@ __all__ = [
     "open_filters", "open_filters_device", "scan_filters", "scan_filters_device",
     "scan_filters_workspace_bytes", "filter_fill", "verify_members", "verify_members_device",
     "verify_members_workspace_bytes", "find_keys", "find_keys_device", "FindResult", "FindCounts",
+    "TreeIndex", "WalkResult", "walk_paths", "walk_paths_device", "walk_paths_workspace_bytes",
 ]

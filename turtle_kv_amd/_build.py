@@ -18,6 +18,7 @@ LIB = os.path.join(HERE, "libtkv_amq.so")
 SOURCES = [os.path.join(HERE, "csrc", "tkv_amq_kernels.hip"),
            os.path.join(HERE, "csrc", "tkv_amq_open_scan.hip"),
            os.path.join(HERE, "csrc", "tkv_amq_find.hip"),
+           os.path.join(HERE, "csrc", "tkv_amq_walk.hip"),
            os.path.join(HERE, "csrc", "tkv_amq_stage.cpp")]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", "tkv_amq_device.h"),
                   os.path.join(HERE, "csrc", "tkv_amq_verify.h"),  # (included by tkv_amq_kernels.hip)

@@ -98,6 +98,7 @@ EXPORTS = [
     "tkv_amq_build_route",
     "tkv_amq_verify_members_ws_bytes", "tkv_amq_verify_members",
     "tkv_amq_find_keys",
+    "tkv_amq_walk_paths_ws_bytes", "tkv_amq_walk_paths",
 ]
 
 # tkv_amq_build_route: TKV_AMQ_ROUTE_* (a Bloom batch's route, or a VQF batch's decide stage),
@@ -148,6 +149,45 @@ FIND_ALL = 0x1
 CAND_ABSENT, CAND_FOUND, CAND_NOT_SEARCHED, CAND_UNSEARCHABLE = range(4)
 NOT_FOUND = (1 << 64) - 1  # key_index of a query whose key no searched candidate holds
 NO_LEAF = 0xFFFFFFFF       # its leaf and cand
+
+
+
+# tkv_amq_walk_paths: the flat tree (tkv_amq_tree_node / _segment / _child) and its limits
+class TreeNode(ctypes.Structure):
+    """tkv_amq_tree_node (32 bytes)."""
+    _fields_ = [("pivot_key_begin", ctypes.c_uint32), ("seg_begin", ctypes.c_uint32),
+                ("child_begin", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),
+                ("pivot_count", ctypes.c_uint8), ("height", ctypes.c_uint8),
+                ("level_count", ctypes.c_uint8), ("reserved1", ctypes.c_uint8),
+                ("level_start", ctypes.c_uint8 * 8), ("reserved2", ctypes.c_uint32)]
+
+
+class TreeSegment(ctypes.Structure):
+    """tkv_amq_tree_segment (32 bytes)."""
+    _fields_ = [("leaf_page_id", ctypes.c_uint64), ("active_pivots", ctypes.c_uint64),
+                ("flushed_pivots", ctypes.c_uint64), ("leaf", ctypes.c_uint32),
+                ("flushed_begin", ctypes.c_uint32)]
+
+
+class TreeChild(ctypes.Structure):
+    """tkv_amq_tree_child (16 bytes)."""
+    _fields_ = [("page_id", ctypes.c_uint64), ("index", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert (ctypes.sizeof(TreeNode), ctypes.sizeof(TreeSegment), ctypes.sizeof(TreeChild)) == (32, 32, 16)
+TREE_NODE_DTYPE = np.dtype([
+    ("pivot_key_begin", "<u4"), ("seg_begin", "<u4"), ("child_begin", "<u4"), ("reserved0", "<u4"),
+    ("pivot_count", "u1"), ("height", "u1"), ("level_count", "u1"), ("reserved1", "u1"),
+    ("level_start", "u1", (8,)), ("reserved2", "<u4")])
+TREE_SEGMENT_DTYPE = np.dtype([
+    ("leaf_page_id", "<u8"), ("active_pivots", "<u8"), ("flushed_pivots", "<u8"), ("leaf", "<u4"),
+    ("flushed_begin", "<u4")])
+TREE_CHILD_DTYPE = np.dtype([("page_id", "<u8"), ("index", "<u4"), ("reserved", "<u4")])
+assert (TREE_NODE_DTYPE.itemsize, TREE_SEGMENT_DTYPE.itemsize, TREE_CHILD_DTYPE.itemsize) == (32, 32, 16)
+WALK_MAX_DEPTH = 16      # TKV_AMQ_WALK_MAX_DEPTH
+WALK_LEAF_LEVEL = 0xFF   # TKV_AMQ_WALK_LEAF_LEVEL: d_path_where's level byte of a child-leaf entry
+# PackedNodePage's limits (tree/packed_node_page.hpp:42-223), which TreeIndex validates
+TREE_MAX_PIVOTS, TREE_MAX_SEGMENTS, TREE_MAX_LEVELS = 64, 63, 7
 
 
 class RoutePlan(ctypes.Structure):
@@ -275,6 +315,12 @@ def lib(build_if_missing: bool = True):
         L.tkv_amq_find_keys.restype = i32
         L.tkv_amq_find_keys.argtypes = [i32, vp, vp, u32, vp, vp, u32, u64, vp, vp, vp, u64, vp, vp, u32,
                                         u64, vp, u32, vp, vp, popts, vp, vp]
+    if hasattr(L, "tkv_amq_walk_paths"):
+        L.tkv_amq_walk_paths_ws_bytes.restype = u64
+        L.tkv_amq_walk_paths_ws_bytes.argtypes = [u64]
+        L.tkv_amq_walk_paths.restype = i32
+        L.tkv_amq_walk_paths.argtypes = [vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, u32, u64, vp, vp, u32,
+                                         u64, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp]
     if hasattr(L, "tkv_amq_bloom_route"):
         L.tkv_amq_bloom_route_ws_bytes.restype = u64
         L.tkv_amq_bloom_route_ws_bytes.argtypes = [u64, u32]

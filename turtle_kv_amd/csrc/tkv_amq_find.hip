@@ -63,29 +63,6 @@ struct FindArgs {
   tkv_amq_find_counts* counts;
 };
 
-__device__ inline uint64_t be64(uint32_t lo, uint32_t hi) { return __builtin_bswap64(mk64(lo, hi)); }
-
-// memcmp order, then the shorter key first (std::string_view's): < 0, 0, > 0 for k <, ==, > q
-__device__ inline int key_compare(const uint8_t* k, uint32_t klen, const uint8_t* q, uint32_t qlen)
-{
-  const uint32_t n = klen < qlen ? klen : qlen;
-  uint32_t o = 0;
-  for (; o + 8 <= n; o += 8) {
-    const uint64_t x = ld64_unaligned(k + o), y = ld64_unaligned(q + o);
-    if (x != y) return __builtin_bswap64(x) < __builtin_bswap64(y) ? -1 : 1;
-  }
-  if (o + 4 <= n) {
-    const uint32_t x = ld32_unaligned(k + o), y = ld32_unaligned(q + o);
-    if (x != y) return __builtin_bswap32(x) < __builtin_bswap32(y) ? -1 : 1;
-    o += 4;
-  }
-  for (; o < n; ++o) {
-    const uint32_t x = k[o], y = q[o];
-    if (x != y) return x < y ? -1 : 1;
-  }
-  return klen < qlen ? -1 : (klen > qlen ? 1 : 0);
-}
-
 // The query of one lane, and its comparison with leaf key `i`.
 template <int MODE>
 struct FindQuery;

@@ -1,0 +1,453 @@
+// tkv_amq_walk.hip -- the tree descent in front of the path probe: tkv_amq_walk_paths.
+//
+//   walk_count_kernel  one lane per query (workgroup tiles of 256, grid-stride).  The lane descends
+//                      from node 0: per node a branch-free upper bound over the interior pivot keys
+//                      (find_pivot_containing, tree/algo/nodes.hpp:48-71), then the active_pivots
+//                      bit sets of the node's segments, level by level (find_key, :158-187;
+//                      for_each_active_segment_in, tree/algo/segmented_levels.hpp:340-369), then
+//                      child p.  It counts the entries, keeps the pivot of every depth in the
+//                      workspace (6 bits x 16 depths) and leaves the tile's exclusive prefix in
+//                      path_begin and the tile's total in the workspace.
+//   walk_scan_totals   one workgroup: the tiles' totals to 64-bit exclusive prefixes; the total.
+//   walk_write_kernel  the same descent with the pivots read back: no key is compared again, only
+//                      nodes, bit sets and children are re-read; entries go to their positions.
+//
+// Both descents are one function (walk_tree) with the pivot source and the entry sink as
+// arguments, so the two passes cannot disagree about a path.  A tree over thousands of leaves is
+// about a hundred nodes: it stays in L2, every step is a dependent L2 read, and the throughput
+// comes from waves in flight.  Every index is checked against its array
+// before the read, so a malformed tree gives a defined answer.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "tkv_amq.h"
+#include "tkv_amq_device.h"
+
+namespace tkv {
+namespace {
+
+constexpr uint32_t kWalkThreads = 256;
+// the tile loop's workgroups at most: one round of a full machine (256 CUs x 8 workgroups)
+constexpr uint32_t kWalkMaxGrid = 2048;
+constexpr uint32_t kWalkScanPerThread = 4;
+constexpr uint32_t kWalkScanSpan = kWalkThreads * kWalkScanPerThread;  // tile totals per scan pass
+constexpr uint32_t kWalkTrailSplit = 10;  // depths 0..9 in the trail's low word, 10..15 in the high
+
+static_assert(sizeof(tkv_amq_tree_node) == 32 && sizeof(tkv_amq_tree_segment) == 32 &&
+                  sizeof(tkv_amq_tree_child) == 16,
+              "tree records");
+static_assert(TKV_AMQ_WALK_MAX_DEPTH == 16, "the trail holds 16 pivots of 6 bits");
+
+// kWalk16: both sides fixed 16-byte keys, 16-byte aligned; kWalk24: both fixed 24-byte keys,
+// 8-byte aligned; kWalkAny: everything else (the modes of tkv_amq_find.hip)
+enum WalkMode : int { kWalk16 = 0, kWalk24 = 1, kWalkAny = 2 };
+
+struct WalkArgs {
+  const tkv_amq_tree_node* nodes;
+  const tkv_amq_tree_segment* segs;
+  const tkv_amq_tree_child* children;
+  const uint32_t* bounds;
+  uint32_t n_nodes, n_segs, n_children, n_bounds;
+  const uint8_t* pk;
+  const uint64_t* pkoffs;
+  uint32_t pkstride;
+  uint32_t n_pk;
+  const uint8_t* q;
+  const uint64_t* qoffs;
+  uint32_t qstride;
+  uint32_t n_queries;
+  uint32_t n_tiles;
+  uint32_t capacity;
+  uint32_t* path_begin;
+  uint32_t* path_leaf;
+  uint64_t* path_page_id;
+  uint32_t* path_flushed;
+  uint16_t* path_where;
+  uint64_t* needed;
+  ulonglong2* trail;     // [n_queries]
+  uint64_t* tile_total;  // [n_tiles]: totals, then their exclusive prefixes
+};
+
+// The query of one lane, and "pivot key i <= query".
+template <int MODE>
+struct WalkQuery;
+
+template <>
+struct WalkQuery<kWalk16> {
+  uint64_t w0, w1;
+  __device__ inline WalkQuery(const WalkArgs& a, uint64_t i)
+  {
+    const uint4 v = *reinterpret_cast<const uint4*>(a.q + 16 * i);
+    w0 = be64(v.x, v.y);
+    w1 = be64(v.z, v.w);
+  }
+  __device__ inline bool key_le(const WalkArgs& a, uint64_t i) const
+  {
+    const uint4 v = *reinterpret_cast<const uint4*>(a.pk + 16 * i);
+    const uint64_t k0 = be64(v.x, v.y), k1 = be64(v.z, v.w);
+    return k0 < w0 || (k0 == w0 && k1 <= w1);
+  }
+};
+
+template <>
+struct WalkQuery<kWalk24> {
+  uint64_t w0, w1, w2;
+  __device__ inline WalkQuery(const WalkArgs& a, uint64_t i)
+  {
+    const uint64_t* p = reinterpret_cast<const uint64_t*>(a.q + 24 * i);
+    w0 = __builtin_bswap64(p[0]);
+    w1 = __builtin_bswap64(p[1]);
+    w2 = __builtin_bswap64(p[2]);
+  }
+  __device__ inline bool key_le(const WalkArgs& a, uint64_t i) const
+  {
+    const uint64_t* p = reinterpret_cast<const uint64_t*>(a.pk + 24 * i);
+    const uint64_t k0 = __builtin_bswap64(p[0]), k1 = __builtin_bswap64(p[1]), k2 = __builtin_bswap64(p[2]);
+    return k0 < w0 || (k0 == w0 && (k1 < w1 || (k1 == w1 && k2 <= w2)));
+  }
+};
+
+template <>
+struct WalkQuery<kWalkAny> {
+  const uint8_t* p;
+  uint32_t len;
+  __device__ inline WalkQuery(const WalkArgs& a, uint64_t i)
+  {
+    if (a.qoffs) {
+      const uint64_t b = a.qoffs[i];
+      p = a.q + b;
+      len = (uint32_t)(a.qoffs[i + 1] - b);
+    } else {
+      p = a.q + i * a.qstride;
+      len = a.qstride;
+    }
+  }
+  __device__ inline bool key_le(const WalkArgs& a, uint64_t i) const
+  {
+    const uint8_t* k;
+    uint32_t klen;
+    if (a.pkoffs) {
+      const uint64_t b = a.pkoffs[i];
+      k = a.pk + b;
+      klen = (uint32_t)(a.pkoffs[i + 1] - b);
+    } else {
+      k = a.pk + i * a.pkstride;
+      klen = a.pkstride;
+    }
+    return key_compare(k, klen, p, len) <= 0;
+  }
+};
+
+// The pivot of the query in a node that owns keys k0..kp from `key_begin`: the number of interior
+// keys k1..k(p-1) that are <= the query (std::upper_bound over them).  k0 and kp are never read;
+// interior keys at or past n_pk do not exist.
+template <int MODE>
+__device__ inline uint32_t find_pivot(const WalkArgs& a, const WalkQuery<MODE>& q, uint32_t key_begin,
+                                      uint32_t pivot_count)
+{
+  const uint64_t first = (uint64_t)key_begin + 1;
+  const uint64_t have = first < a.n_pk ? a.n_pk - first : 0;
+  uint32_t len = pivot_count - 1;
+  len = have < len ? (uint32_t)have : len;
+  // branch-free: lanes in nodes of equal fan-out take the same trip count (at most 6)
+  uint64_t b = first;
+  while (len > 1) {
+    const uint32_t half = len >> 1;
+    b += q.key_le(a, b + half - 1) ? half : 0;
+    len -= half;
+  }
+  if (len == 1) b += q.key_le(a, b) ? 1 : 0;
+  return (uint32_t)(b - first);
+}
+
+// The pivots of one walk, 6 bits per depth.
+struct Trail {
+  uint64_t lo = 0, hi = 0;
+  __device__ inline void put(uint32_t depth, uint32_t p)
+  {
+    if (depth < kWalkTrailSplit) lo |= (uint64_t)p << (6 * depth);
+    else hi |= (uint64_t)p << (6 * (depth - kWalkTrailSplit));
+  }
+  __device__ inline uint32_t get(uint32_t depth) const
+  {
+    const uint64_t w = depth < kWalkTrailSplit ? lo >> (6 * depth) : hi >> (6 * (depth - kWalkTrailSplit));
+    return (uint32_t)w & 63u;
+  }
+};
+
+// One query's descent.  pivot(depth, key_begin, pivot_count) names the pivot; entry(seg index, p,
+// where) is called for every segment active for it, leaf(index, page id, where) for the child leaf.
+template <class Pivot, class Entry, class Leaf>
+__device__ inline void walk_tree(const WalkArgs& a, Pivot&& pivot, Entry&& entry, Leaf&& leaf)
+{
+  uint32_t ni = 0;
+  for (uint32_t depth = 0; depth < TKV_AMQ_WALK_MAX_DEPTH; ++depth) {
+    if (ni >= a.n_nodes) return;
+    const uint4* np = reinterpret_cast<const uint4*>(a.nodes + ni);
+    const uint4 n0 = np[0], n1 = np[1];  // {pivot_key_begin, seg_begin, child_begin, -}, {counts, level_start, -}
+    const uint32_t pivot_count = n1.x & 0xffu, height = (n1.x >> 8) & 0xffu;
+    const uint32_t level_count = min((n1.x >> 16) & 0xffu, 7u);
+    if (pivot_count == 0 || pivot_count > 64) return;
+    const uint32_t p = pivot(depth, n0.x, pivot_count);
+    const uint64_t bit = 1ull << p;
+    const uint64_t level_start = mk64(n1.y, n1.z);
+    for (uint32_t l = 0; l < level_count; ++l) {
+      // (64-bit sums cannot wrap; a decreasing level_start gives end <= begin: an empty level)
+      const uint64_t lb = (uint64_t)n0.y + ((level_start >> (8 * l)) & 0xffu);
+      const uint64_t le = (uint64_t)n0.y + ((level_start >> (8 * l + 8)) & 0xffu);
+      const uint32_t sb = (uint32_t)min(lb, (uint64_t)a.n_segs), se = (uint32_t)min(le, (uint64_t)a.n_segs);
+      for (uint32_t s = sb; s < se; ++s)
+        if (a.segs[s].active_pivots & bit) entry(s, p, (depth << 8) | l);
+    }
+    const uint64_t c = (uint64_t)n0.z + p;
+    if (c >= a.n_children) return;
+    const uint4 ch = *reinterpret_cast<const uint4*>(a.children + c);  // {page_id, index, -}
+    if (height <= 1) {
+      leaf(ch.z, mk64(ch.x, ch.y), (depth << 8) | TKV_AMQ_WALK_LEAF_LEVEL);
+      return;
+    }
+    ni = ch.z;
+  }
+}
+
+// exclusive scan of v over the workgroup's 256 threads; *total = the sum.  s: 4 words of LDS.
+template <class T>
+__device__ inline T walk_block_scan(T v, T* s, T* total)
+{
+  const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
+  T x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T y = __shfl_up(x, o, 64);
+    if (lane >= (uint32_t)o) x += y;
+  }
+  __syncthreads();  // (the previous use of s is over)
+  if (lane == 63) s[wave] = x;
+  __syncthreads();
+  T base = 0, sum = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kWalkThreads / 64; ++w) {
+    const T t = s[w];
+    if (w < wave) base += t;
+    sum += t;
+  }
+  *total = sum;
+  return base + x - v;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kWalkThreads) void walk_count_kernel(WalkArgs a)
+{
+  __shared__ uint32_t s_scan[kWalkThreads / 64];
+  for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x) {
+    const uint64_t i = (uint64_t)t * kWalkThreads + threadIdx.x;
+    const bool live = i < a.n_queries;
+    uint32_t cnt = 0;
+    if (live) {
+      const WalkQuery<MODE> q(a, i);
+      Trail trail;
+      walk_tree(
+          a,
+          [&](uint32_t depth, uint32_t key_begin, uint32_t pivot_count) {
+            const uint32_t p = find_pivot<MODE>(a, q, key_begin, pivot_count);
+            trail.put(depth, p);
+            return p;
+          },
+          [&](uint32_t, uint32_t, uint32_t) { ++cnt; }, [&](uint32_t, uint64_t, uint32_t) { ++cnt; });
+      a.trail[i] = ulonglong2{trail.lo, trail.hi};
+    }
+    uint32_t total;
+    const uint32_t pre = walk_block_scan<uint32_t>(cnt, s_scan, &total);
+    if (live) a.path_begin[i] = pre;
+    if (threadIdx.x == 0) a.tile_total[t] = total;
+  }
+}
+
+// One workgroup: tile_total[t] <- the sum of the tiles before t, kWalkScanSpan of them per pass
+// with the running base carried over; path_begin[n_queries] <- min(total, capacity); *needed <-
+// the total.  (n_tiles == 0: an empty batch.)
+__global__ __launch_bounds__(kWalkThreads) void walk_scan_totals(uint64_t* __restrict__ tile_total,
+                                                                 uint32_t n_tiles,
+                                                                 uint32_t* __restrict__ path_begin,
+                                                                 uint32_t n_queries, uint32_t capacity,
+                                                                 uint64_t* __restrict__ needed)
+{
+  __shared__ uint64_t s[kWalkThreads / 64];
+  const uint32_t tid = threadIdx.x;
+  uint64_t base = 0;
+  for (uint32_t p0 = 0; p0 < n_tiles; p0 += kWalkScanSpan) {
+    uint64_t v[kWalkScanPerThread];
+    uint64_t sum = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kWalkScanPerThread; ++r) {
+      const uint64_t t = (uint64_t)p0 + tid * kWalkScanPerThread + r;
+      v[r] = t < n_tiles ? tile_total[t] : 0ull;
+      sum += v[r];
+    }
+    uint64_t total;
+    uint64_t run = base + walk_block_scan<uint64_t>(sum, s, &total);
+#pragma unroll
+    for (uint32_t r = 0; r < kWalkScanPerThread; ++r) {
+      const uint64_t t = (uint64_t)p0 + tid * kWalkScanPerThread + r;
+      if (t < n_tiles) tile_total[t] = run;
+      run += v[r];
+    }
+    base += total;
+  }
+  if (tid == 0) {
+    if (path_begin) path_begin[n_queries] = (uint32_t)min(base, (uint64_t)capacity);
+    if (needed) *needed = base;
+  }
+}
+
+__global__ __launch_bounds__(kWalkThreads) void walk_write_kernel(WalkArgs a)
+{
+  for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x) {
+    const uint64_t i = (uint64_t)t * kWalkThreads + threadIdx.x;
+    if (i >= a.n_queries) continue;
+    uint64_t pos = a.tile_total[t] + a.path_begin[i];
+    a.path_begin[i] = (uint32_t)min(pos, (uint64_t)a.capacity);
+    if (pos >= a.capacity) continue;  // (every entry of this query lies past the capacity)
+    const ulonglong2 tv = a.trail[i];
+    Trail trail;
+    trail.lo = tv.x;
+    trail.hi = tv.y;
+    auto put = [&](uint32_t leaf, uint64_t page_id, uint32_t flushed, uint32_t where) {
+      if (pos < a.capacity) {
+        a.path_leaf[pos] = leaf;
+        if (a.path_page_id) a.path_page_id[pos] = page_id;
+        if (a.path_flushed) a.path_flushed[pos] = flushed;
+        if (a.path_where) a.path_where[pos] = (uint16_t)where;
+      }
+      ++pos;
+    };
+    walk_tree(
+        a, [&](uint32_t depth, uint32_t, uint32_t) { return trail.get(depth); },
+        [&](uint32_t s, uint32_t p, uint32_t where) {
+          const uint4* sp = reinterpret_cast<const uint4*>(a.segs + s);
+          const uint4 s0 = sp[0], s1 = sp[1];  // {leaf_page_id, active}, {flushed, leaf, flushed_begin}
+          const uint64_t flushed = mk64(s1.x, s1.y);
+          uint32_t bound = 0;
+          if (a.path_flushed && ((flushed >> p) & 1u)) {
+            // bit_rank: the set bits of flushed_pivots below p
+            const uint64_t at = (uint64_t)s1.w + (uint32_t)__popcll(flushed & ((1ull << p) - 1));
+            if (at < a.n_bounds) bound = a.bounds[at];
+          }
+          put(s1.z, mk64(s0.x, s0.y), bound, where);
+        },
+        [&](uint32_t index, uint64_t page_id, uint32_t where) { put(index, page_id, 0u, where); });
+  }
+}
+
+struct WalkWsLayout {
+  uint64_t n_tiles, totals_off, trail_off, bytes;
+};
+
+inline WalkWsLayout walk_ws_layout(uint64_t n_queries)
+{
+  WalkWsLayout l;
+  l.n_tiles = (n_queries + kWalkThreads - 1) / kWalkThreads;
+  l.trail_off = 16;
+  l.totals_off = l.trail_off + 16 * n_queries;
+  l.bytes = l.totals_off + (8 * l.n_tiles + 15) / 16 * 16;
+  return l;
+}
+
+}  // namespace
+}  // namespace tkv
+
+using namespace tkv;
+
+extern "C" {
+
+uint64_t tkv_amq_walk_paths_ws_bytes(uint64_t n_queries)
+{
+  if (n_queries > 0xffffffffull) return 0;
+  return walk_ws_layout(n_queries).bytes;
+}
+
+int tkv_amq_walk_paths(const tkv_amq_tree_node* nodes, uint64_t n_nodes, const tkv_amq_tree_segment* segments,
+                       uint64_t n_segments, const tkv_amq_tree_child* children, uint64_t n_children,
+                       const uint32_t* d_flushed_bounds, uint64_t n_flushed_bounds, const uint8_t* pivot_keys,
+                       const uint64_t* pivot_key_offsets, uint32_t pivot_key_stride, uint64_t n_pivot_keys,
+                       const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
+                       uint64_t n_queries, uint32_t* d_path_begin, uint32_t* d_path_leaf,
+                       uint64_t* d_path_page_id, uint32_t* d_path_flushed, uint16_t* d_path_where,
+                       uint64_t path_capacity, uint64_t* d_needed, void* d_workspace, uint64_t workspace_bytes,
+                       void* stream)
+{
+  // (the arguments are judged first, so a bad call is InvalidArgument with or without a device)
+  constexpr uint64_t kMax = 0xffffffffull;
+  if (n_nodes > kMax || n_segments > kMax || n_children > kMax || n_flushed_bounds > kMax ||
+      n_pivot_keys > kMax || n_queries > kMax || path_capacity > kMax)
+    return TKV_AMQ_INVALID_ARGUMENT;
+  if ((n_nodes && !nodes) || (n_segments && !segments) || (n_children && !children) ||
+      (n_flushed_bounds && !d_flushed_bounds) || (n_pivot_keys && !pivot_keys))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  if (n_queries && (!queries || !d_path_begin || !d_workspace)) return TKV_AMQ_INVALID_ARGUMENT;
+  if (path_capacity && !d_path_leaf) return TKV_AMQ_INVALID_ARGUMENT;
+  if ((!pivot_key_offsets && !pivot_key_stride) || (!query_offsets && !query_stride))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  if (((reinterpret_cast<uintptr_t>(nodes) | reinterpret_cast<uintptr_t>(segments) |
+        reinterpret_cast<uintptr_t>(children) | reinterpret_cast<uintptr_t>(d_workspace)) & 15) ||
+      (reinterpret_cast<uintptr_t>(d_needed) & 7))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  const WalkWsLayout l = walk_ws_layout(n_queries);
+  if (n_queries && workspace_bytes < l.bytes) return TKV_AMQ_INVALID_ARGUMENT;
+  if (tkv_amq_device_count() == 0) return TKV_AMQ_UNAVAILABLE;
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 block(kWalkThreads);
+  if (n_queries == 0) {
+    if (d_path_begin || d_needed) {
+      hipLaunchKernelGGL(walk_scan_totals, dim3(1), block, 0, s, static_cast<uint64_t*>(nullptr), 0u,
+                         d_path_begin, 0u, 0u, d_needed);
+      return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
+    }
+    return TKV_AMQ_OK;
+  }
+  uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+  WalkArgs a;
+  a.nodes = nodes;
+  a.segs = segments;
+  a.children = children;
+  a.bounds = d_flushed_bounds;
+  a.n_nodes = (uint32_t)n_nodes;
+  a.n_segs = (uint32_t)n_segments;
+  a.n_children = (uint32_t)n_children;
+  a.n_bounds = (uint32_t)n_flushed_bounds;
+  a.pk = pivot_keys;
+  a.pkoffs = pivot_key_offsets;
+  a.pkstride = pivot_key_stride;
+  a.n_pk = (uint32_t)n_pivot_keys;
+  a.q = queries;
+  a.qoffs = query_offsets;
+  a.qstride = query_stride;
+  a.n_queries = (uint32_t)n_queries;
+  a.n_tiles = (uint32_t)l.n_tiles;
+  a.capacity = (uint32_t)path_capacity;
+  a.path_begin = d_path_begin;
+  a.path_leaf = d_path_leaf;
+  a.path_page_id = d_path_page_id;
+  a.path_flushed = d_path_flushed;
+  a.path_where = d_path_where;
+  a.needed = d_needed;
+  a.trail = reinterpret_cast<ulonglong2*>(ws + l.trail_off);
+  a.tile_total = reinterpret_cast<uint64_t*>(ws + l.totals_off);
+  // the fast modes, chosen as tkv_amq_find_keys chooses them
+  const bool fixed = !query_offsets && !pivot_key_offsets && query_stride == pivot_key_stride;
+  const uintptr_t both = reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(pivot_keys);
+  const int mode = fixed && query_stride == 16 && !(both & 15) ? kWalk16
+                   : fixed && query_stride == 24 && !(both & 7) ? kWalk24
+                                                                : kWalkAny;
+  const dim3 grid(a.n_tiles < kWalkMaxGrid ? a.n_tiles : kWalkMaxGrid);
+  if (mode == kWalk16) hipLaunchKernelGGL(walk_count_kernel<kWalk16>, grid, block, 0, s, a);
+  else if (mode == kWalk24) hipLaunchKernelGGL(walk_count_kernel<kWalk24>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(walk_count_kernel<kWalkAny>, grid, block, 0, s, a);
+  hipLaunchKernelGGL(walk_scan_totals, dim3(1), block, 0, s, a.tile_total, a.n_tiles, d_path_begin,
+                     a.n_queries, a.capacity, d_needed);
+  hipLaunchKernelGGL(walk_write_kernel, grid, block, 0, s, a);
+  return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
+}
+
+}  // extern "C"

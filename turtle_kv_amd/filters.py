@@ -1063,6 +1063,223 @@ def find_keys(plan_or_opened, filters, queries: KeyBatch, cands, leaf_keys: KeyB
     lc = raw[:16 * queries.n].view(torch.int32).view(queries.n, 4)
     return FindResult(rec[:, 0], lc[:, 2], lc[:, 3], state, raw)
 
+
+# ---------------------------------------------------------------------------------------
+# tree walk: resolve each lookup to the path the probe and the search start from
+# ---------------------------------------------------------------------------------------
+class TreeIndex:
+    """The flat tree tkv_amq_walk_paths descends, built on the host from a nested description and
+    uploaded once.
+
+    A node is a dict: "pivot_keys": its pivot_count + 1 keys k0..kp (bytes; k0 and kp bound the
+    node and are never compared), "children": one per pivot -- all nodes, or all leaves
+    {"leaf": plan segment index, "page_id": int} --, "levels": the update buffer, newest first,
+    each a list of segments {"leaf": int, "page_id": int, "active": bit set of pivots,
+    "flushed": {pivot: flushed item upper bound}}, and "page_id" (the root's is not stored).
+    The limits are PackedNodePage's (tree/packed_node_page.hpp:42-223): at most 64 pivots and 63
+    segments per node; levels: the 7 the flat record holds (the reference's page holds 6).  Node 0
+    is the root; nodes are numbered breadth first."""
+
+    def __init__(self, nodes, segments, children, flushed_bounds, pivot_keys):
+        self.nodes = np.ascontiguousarray(nodes, dtype=abi.TREE_NODE_DTYPE)
+        self.segments = np.ascontiguousarray(segments, dtype=abi.TREE_SEGMENT_DTYPE)
+        self.children = np.ascontiguousarray(children, dtype=abi.TREE_CHILD_DTYPE)
+        self.flushed_bounds = np.ascontiguousarray(flushed_bounds, dtype=np.uint32)
+        self.pivot_keys = [bytes(k) for k in pivot_keys]
+        self._device = {}
+
+    @staticmethod
+    def _check_node(node, height_of):
+        keys, kids, levels = node["pivot_keys"], node["children"], node.get("levels", [])
+        n = len(kids)
+        if not 1 <= n <= abi.TREE_MAX_PIVOTS:
+            raise ValueError(f"a node has 1..{abi.TREE_MAX_PIVOTS} pivots, not {n}")
+        if len(keys) != n + 1:
+            raise ValueError(f"a node of {n} pivots owns {n + 1} pivot keys, not {len(keys)}")
+        if len(levels) > abi.TREE_MAX_LEVELS:
+            raise ValueError(f"a node has at most {abi.TREE_MAX_LEVELS} levels, not {len(levels)}")
+        n_seg = sum(len(lv) for lv in levels)
+        if n_seg > abi.TREE_MAX_SEGMENTS:
+            raise ValueError(f"a node has at most {abi.TREE_MAX_SEGMENTS} segments, not {n_seg}")
+        kinds = {"pivot_keys" in c for c in kids}
+        if len(kinds) != 1:
+            raise ValueError("a node's children are all nodes or all leaves")
+        heights = {height_of(c) for c in kids}
+        if len(heights) != 1:
+            raise ValueError("a node's children have one height")
+        for lv in levels:
+            for s in lv:
+                if int(s.get("active", 0)) >> n or any(not 0 <= int(p) < n for p in s.get("flushed", {})):
+                    raise ValueError("a segment names a pivot the node does not have")
+        return heights.pop() + 1
+
+    @classmethod
+    def from_description(cls, root) -> "TreeIndex":
+        heights = {}
+
+        def height_of(d):
+            if "pivot_keys" not in d:
+                return 0
+            if id(d) not in heights:
+                heights[id(d)] = cls._check_node(d, height_of)
+            return heights[id(d)]
+
+        if height_of(root) > abi.WALK_MAX_DEPTH:
+            raise ValueError(f"a tree has at most {abi.WALK_MAX_DEPTH} levels of nodes")
+        order, at = [root], 0
+        while at < len(order):  # breadth first: a node's children get consecutive numbers
+            order.extend(c for c in order[at]["children"] if "pivot_keys" in c)
+            at += 1
+        number = {id(d): i for i, d in enumerate(order)}
+        nodes = np.zeros(len(order), dtype=abi.TREE_NODE_DTYPE)
+        segs, kids, bounds, keys = [], [], [], []
+        for i, d in enumerate(order):
+            levels = d.get("levels", [])
+            nd = nodes[i]
+            nd["pivot_key_begin"], nd["seg_begin"], nd["child_begin"] = len(keys), len(segs), len(kids)
+            nd["pivot_count"], nd["height"], nd["level_count"] = len(d["children"]), heights[id(d)], len(levels)
+            start = np.cumsum([0] + [len(lv) for lv in levels])
+            nd["level_start"][:len(start)] = start
+            nd["level_start"][len(start):] = start[-1]
+            keys.extend(bytes(k) for k in d["pivot_keys"])
+            for c in d["children"]:
+                kids.append((int(c.get("page_id", 0)), number[id(c)] if "pivot_keys" in c else int(c["leaf"]), 0))
+            for lv in levels:
+                for s in lv:
+                    fl = {int(p): int(b) for p, b in s.get("flushed", {}).items()}
+                    segs.append((int(s.get("page_id", 0)), int(s.get("active", 0)),
+                                 sum(1 << p for p in fl), int(s["leaf"]), len(bounds)))
+                    bounds.extend(fl[p] for p in sorted(fl))
+        return cls(nodes, np.array(segs, dtype=abi.TREE_SEGMENT_DTYPE),
+                   np.array(kids, dtype=abi.TREE_CHILD_DTYPE), np.array(bounds, dtype=np.uint32), keys)
+
+    def describe(self, node: int = 0, page_id: int = 0) -> dict:
+        """The nested description of the subtree under `node` (from_description's inverse)."""
+        nd = self.nodes[node]
+        n, kb, sb, cb = int(nd["pivot_count"]), int(nd["pivot_key_begin"]), int(nd["seg_begin"]), \
+            int(nd["child_begin"])
+        levels = []
+        for lv in range(int(nd["level_count"])):
+            level = []
+            for s in self.segments[sb + int(nd["level_start"][lv]):sb + int(nd["level_start"][lv + 1])]:
+                fp, fb = int(s["flushed_pivots"]), int(s["flushed_begin"])
+                pivots = [p for p in range(64) if fp >> p & 1]
+                level.append({"leaf": int(s["leaf"]), "page_id": int(s["leaf_page_id"]),
+                              "active": int(s["active_pivots"]),
+                              "flushed": {p: int(self.flushed_bounds[fb + r]) for r, p in enumerate(pivots)}})
+            levels.append(level)
+        kids = []
+        for c in self.children[cb:cb + n]:
+            if int(nd["height"]) > 1:
+                kids.append(self.describe(int(c["index"]), int(c["page_id"])))
+            else:
+                kids.append({"leaf": int(c["index"]), "page_id": int(c["page_id"])})
+        return {"pivot_keys": self.pivot_keys[kb:kb + n + 1], "children": kids, "levels": levels,
+                "page_id": page_id}
+
+    def pivot_key_batch(self, device=None) -> KeyBatch:
+        return KeyBatch.from_host(self.pivot_keys, device)
+
+    def device(self, device=None):
+        """(nodes, segments, children, flushed_bounds, pivot keys) on the device: uint8 views of the
+        records, int32 bounds and a KeyBatch; uploaded once per device."""
+        torch = _torch()
+        dev = torch.device(device or "cuda")
+        if dev not in self._device:
+            def up(a):
+                raw = np.frombuffer(a.tobytes(), dtype=np.uint8)
+                return torch.from_numpy(raw.copy() if len(raw) else np.zeros(16, np.uint8)).to(dev)
+            b = self.flushed_bounds.view(np.int32)
+            self._device[dev] = (up(self.nodes), up(self.segments), up(self.children),
+                                 torch.from_numpy(b.copy() if len(b) else np.zeros(1, np.int32)).to(dev),
+                                 self.pivot_key_batch(dev))
+        return self._device[dev]
+
+
+def walk_paths_workspace_bytes(n_queries: int) -> int:
+    """Device workspace tkv_amq_walk_paths needs (host only; 0 for counts it refuses)."""
+    return int(abi.lib().tkv_amq_walk_paths_ws_bytes(int(n_queries)))
+
+
+@dataclass
+class WalkResult:
+    """What walk_paths leaves on the device: query i's path is entries
+    [path_begin[i], path_begin[i+1]) of path_leaf (plan segment indices, in lookup order) and of
+    each optional array; only entries below min(needed, capacity) are written."""
+    path_begin: object                   # int32 [n_queries + 1]
+    path_leaf: object                    # int32 [capacity]
+    path_page_id: object = None          # int64 [capacity], or None
+    path_flushed: object = None          # int32 [capacity], or None
+    path_where: object = None            # int16 [capacity] (depth << 8 | level), or None
+    needed: object = None                # int64 [1]: the unclamped total
+    capacity: int = 0
+    workspace: object = field(default=None, repr=False)
+
+    def total(self) -> int:
+        """Number of entries written (synchronises)."""
+        return int(self.path_begin[-1].item())
+
+
+def walk_paths_device(d_nodes, n_nodes: int, d_segments, n_segments: int, d_children, n_children: int,
+                      d_flushed_bounds, n_flushed_bounds: int, pivot_keys, pivot_key_offsets,
+                      pivot_key_stride: int, n_pivot_keys: int, queries, query_offsets, query_stride: int,
+                      n_queries: int, d_path_begin, d_path_leaf, path_capacity: int, workspace,
+                      d_path_page_id=None, d_path_flushed=None, d_path_where=None, d_needed=None,
+                      stream=None) -> None:
+    """The launch alone (tkv_amq_walk_paths), capturable in front of probe_paths: raw device tensors
+    in, nothing allocated, nothing copied back."""
+    _require_device()
+    st = abi.lib().tkv_amq_walk_paths(
+        _ptr(d_nodes), int(n_nodes), _ptr(d_segments), int(n_segments), _ptr(d_children), int(n_children),
+        _ptr(d_flushed_bounds), int(n_flushed_bounds), _ptr(pivot_keys), _ptr(pivot_key_offsets),
+        int(pivot_key_stride), int(n_pivot_keys), _ptr(queries), _ptr(query_offsets), int(query_stride),
+        int(n_queries), _ptr(d_path_begin), _ptr(d_path_leaf), _ptr(d_path_page_id), _ptr(d_path_flushed),
+        _ptr(d_path_where), int(path_capacity), _ptr(d_needed), _ptr(workspace),
+        0 if workspace is None else int(workspace.numel()), _stream_handle(stream))
+    abi.check(st, "tkv_amq_walk_paths")
+
+
+def walk_paths(tree: TreeIndex, queries: KeyBatch, capacity: int | None = None, want_page_ids: bool = False,
+               want_flushed: bool = False, want_where: bool = False, workspace=None,
+               stream=None) -> WalkResult:
+    """Each query's ordered list of leaves (tkv_amq_walk_paths): the CSR list probe_paths and
+    find_keys start from.  With a `capacity` the call is asynchronous; entries past it are counted
+    in `needed` and not written.  capacity=None is the one synchronising convenience: the walk runs
+    once with capacity 0, `needed` is read back, and it runs again with exactly that capacity."""
+    torch = _torch()
+    _require_device()
+    dev = queries.data.device
+    d_nodes, d_segs, d_kids, d_bounds, pk = tree.device(dev)
+    need = walk_paths_workspace_bytes(queries.n)
+    if need == 0:
+        raise TkvAmqError(abi.INVALID_ARGUMENT, "tkv_amq_walk_paths: too many queries")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    begin = torch.empty(queries.n + 1, dtype=torch.int32, device=dev)
+    needed = torch.empty(1, dtype=torch.int64, device=dev)
+
+    def run(cap, leaf, page, flushed, where):
+        walk_paths_device(d_nodes, len(tree.nodes), d_segs, len(tree.segments), d_kids, len(tree.children),
+                          d_bounds, len(tree.flushed_bounds), pk.data, pk.offsets, pk.stride, pk.n,
+                          queries.data, queries.offsets, queries.stride, queries.n, begin, leaf, cap,
+                          workspace, page, flushed, where, needed, stream)
+
+    if capacity is None:
+        run(0, None, None, None, None)
+        if stream is not None:
+            stream.synchronize()
+        capacity = int(needed.item())
+    capacity = int(capacity)
+    leaf = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
+    page = torch.empty(max(capacity, 1), dtype=torch.int64, device=dev) if want_page_ids else None
+    flushed = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev) if want_flushed else None
+    where = torch.empty(max(capacity, 1), dtype=torch.int16, device=dev) if want_where else None
+    run(capacity, leaf, page, flushed, where)
+    _hold(stream, workspace, begin, needed, leaf, page, flushed, where)
+    return WalkResult(begin, leaf[:capacity], None if page is None else page[:capacity],
+                      None if flushed is None else flushed[:capacity],
+                      None if where is None else where[:capacity], needed, capacity, workspace)
+
 # ---------------------------------------------------------------------------------------
 # single-leaf API (the reference's per-leaf entry points)
 # ---------------------------------------------------------------------------------------
