@@ -253,7 +253,8 @@ struct tkv_amq_build_route { /* 40 bytes */
   uint32_t threads;       /* the build kernel's workgroup size (VQF: the decide stage's) */
   uint32_t located;       /* VQF: vqf_locate_keys runs ahead of vqf_ring_place */
   uint64_t ws_bytes;      /* the workspace the route needs */
-  uint32_t lds_bytes;     /* Bloom: a workgroup's LDS image (0: tiled, atomics); VQF: the decide
+  uint32_t lds_bytes;     /* Bloom: a workgroup's LDS image, 64 bytes a block (0: tiled, atomics; the
+                             launch takes whole 512-byte regions of 8 blocks); VQF: the decide
                              stage's dynamic LDS */
   uint32_t reserved;
 };

@@ -42,6 +42,7 @@
 
 #include "tkv_amq.h"
 #include "tkv_amq_device.h"
+#include "tkv_amq_lds_stride.h"
 
 // The one diagnostic build option (TKV_DIAG_RING: per-step timestamps of vqf_ring_place's
 // decider, read by tools/ring_diag.py) is for experiment libraries only; the shipped library
@@ -245,30 +246,103 @@ __device__ inline uint32_t lds_addr(const void* p)
 }
 TKV_INLINE uint32_t* lds_ptr(uint32_t a) { return (uint32_t*)reinterpret_cast<lds_u32_t*>((uintptr_t)a); }
 
+// The strided image (tkv_amq_lds_stride.h): the word number of a bit sits at address bits 5..8,
+// where the bit index has it.  Per key, lds_stride_key4 forms X = image base + the local block's
+// region and slot, with bits 5..8 left as they fall.  It takes the block times four, b4, whose
+// bits 0..1 may hold anything: v_lshl_add_u32 puts the block at bit 6 (its region lands at bit 9,
+// its slot and b4's low bits in the don't-care bits 4..8), v_bfi_b32 0x1c puts the slot, b4's bits
+// 2..4 as they stand, over bits 2..4.  Per bit, lds_set_bit_strided inserts the bit index's bits
+// 5..8 into X (one v_bfi_b32; the shift takes bits 0..4): two VALU a bit where the canonical
+// image takes three.  The image base must be kStrideRegionBytes-aligned: the kernels declare
+// their dynamic LDS so, and check the offset of an image that does not start it.  Both v_bfi are
+// asm: spelled in C++ the compiler is free to re-split them into and / or.
+TKV_INLINE uint32_t lds_stride_key4(uint32_t image_base, uint32_t b4)
+{
+  const uint32_t t = (b4 << 4) + image_base;
+  uint32_t x;
+  asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(x) : "n"(kStrideSlotMask), "v"(b4), "v"(t));
+  return x;
+}
+TKV_INLINE uint32_t lds_stride_key(uint32_t image_base, uint32_t local_block)
+{
+  return lds_stride_key4(image_base, local_block << 2);
+}
+
+TKV_INLINE void lds_set_bit_strided(uint32_t x, uint32_t bit)
+{
+  // `bit`: bits 0..8 are the index, higher bits are ignored (the mask is past the inline
+  // constants: it is held in an SGPR)
+  uint32_t a;
+  asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(a) : "s"(kStrideWordMask), "v"(bit), "v"(x));
+  atomicOr(lds_ptr(a), 1u << (bit & 31));
+}
+
+// Zeroes the strided image of nb blocks: whole regions, ceil(nb / 8) * 128 words.
+template <uint32_t NT>
+TKV_INLINE void lds_stride_zero(uint32_t* s_bits, uint32_t nb)
+{
+  const uint32_t nq = lds_stride_words(nb) / 4;  // (16 bytes a store: the image is region-aligned)
+  uint4* img = reinterpret_cast<uint4*>(s_bits);
+  for (uint32_t q = threadIdx.x; q < nq; q += NT) img[q] = make_uint4(0, 0, 0, 0);
+}
+
+// Writes the strided image of nb blocks to dst in canonical order, 16 bytes a lane: output quad q
+// (words 4 * (q & 3) .. + 3 of block q >> 2) is four words 32 bytes apart.  From one quad of a
+// lane to its next (q + NT: NT / 32 regions on) the address advances by NT * 16 bytes, so the loop
+// carries one address.  For one of the four reads a wave's 64 quads (16 blocks, two regions) fall
+// on 16 banks, 8 slots x 2 rows, whatever lane takes which quad: the row is 4 * (q & 3) + i, and
+// only a per-lane i would spread it, at 8 v_cndmask a quad to put the words back in order.  The
+// kernel is VALU-bound and reads 1 word here per 22 ds_or, so the lanes keep q = tid and the order.
+template <uint32_t NT>
+TKV_INLINE void lds_stride_write_out(uint32_t* s_bits, uint32_t nb, uint4* __restrict__ dst)
+{
+  static_assert(NT % (4 * kStrideRegionBlocks) == 0, "a lane's quads must keep their slot and row");
+  const uint32_t tid = threadIdx.x, nq = nb * 4;
+  uint32_t a = lds_addr(s_bits) + lds_stride_quad(tid);
+  for (uint32_t q = tid; q < nq; q += NT, a += NT * 16) {
+    const uint32_t* p = lds_ptr(a);
+    constexpr uint32_t W = kStrideWordBytes / 4;
+    dst[q] = make_uint4(p[0], p[W], p[2 * W], p[3 * W]);
+  }
+}
+
 // Every bit of one hashed key into an LDS image whose first block is `first` (a tile image's).
 // The block is below 2^32 and the image base is a 32-bit LDS address, so the block's address is
 // one shift-add (spelled in 64 bits the compiler keeps a 64-bit shift and a mask); `first` moves
 // the wave-uniform base, not the block.  Bit 0 goes in unmasked, as the ladder's bits do.
-template <int K, bool kMask = false, typename H>
+// kStride: s_bits is a strided image (the leaf, split and window builds).  The hash is scaled by
+// 4 * nb instead of nb: floor(4 x) >> 2 == floor(x), so the product's high word is the block
+// times four plus two bits nobody reads, which is the form lds_stride_key4 takes: the per-key
+// base costs two VALU (nb < 2^30: an image in LDS has at most 2,560 blocks).  The local block,
+// block - first, is formed before it is split into region and slot.  The canonical image is the
+// default: the tile builds and every records-based path keep it.
+template <int K, bool kMask = false, bool kStride = false, typename H>
 TKV_INLINE void bloom_insert(uint32_t* s_bits, uint32_t nb, uint32_t k, const H& x, uint32_t first = 0)
 {
   const uint64_t h0 = x.h0();
-  uint32_t block = (uint32_t)bloom_block(h0, nb);
+  uint32_t block = (uint32_t)bloom_block(h0, kStride ? nb * 4u : nb);
   // (opaque: LLVM otherwise folds the shift into the 64-bit product, v_alignbit 26 + v_and + v_add)
   asm("" : "+v"(block));
-  uint32_t* blk = lds_ptr((block << 6) + (lds_addr(s_bits) - (first << 6)));
-  lds_set_bit(blk, (uint32_t)h0);
-  bloom_ladder<K>(x, k, [&](uint32_t, uint32_t b) { lds_set_bit(blk, kMask ? b & kBloomBitMask : b); });
+  if constexpr (kStride) {
+    const uint32_t sx = lds_stride_key4(lds_addr(s_bits), block - first * 4u);
+    lds_set_bit_strided(sx, (uint32_t)h0);
+    bloom_ladder<K>(x, k, [&](uint32_t, uint32_t b) { lds_set_bit_strided(sx, b); });
+  } else {
+    uint32_t* blk = lds_ptr((block << 6) + (lds_addr(s_bits) - (first << 6)));
+    lds_set_bit(blk, (uint32_t)h0);
+    bloom_ladder<K>(x, k, [&](uint32_t, uint32_t b) { lds_set_bit(blk, kMask ? b & kBloomBitMask : b); });
+  }
 }
 
-// Bloom insert of one fixed/variable-length key: keys under 32 bytes share the seed-independent
-// lane rounds over all k hashes (BloomShort); longer keys hash from scratch per seed.
+// Bloom insert of one fixed/variable-length key into a strided image: keys under 32 bytes share
+// the seed-independent lane rounds over all k hashes (BloomShort); longer keys hash from scratch
+// per seed.
 template <int K, int MODE>
 __device__ inline void bloom_insert_any(uint32_t* s_bits, uint32_t nb, uint32_t k,
                                         const uint8_t* p, uint32_t len)
 {
-  if (len < 32) bloom_insert<K>(s_bits, nb, k, BloomShort(p, len));
-  else bloom_insert<0, true>(s_bits, nb, k, BloomLong{p, len});  // (kMask: the parent's v_and stays)
+  if (len < 32) bloom_insert<K, false, true>(s_bits, nb, k, BloomShort(p, len));
+  else bloom_insert<0, false, true>(s_bits, nb, k, BloomLong{p, len});
 }
 
 __device__ inline void write_bloom_header(uint8_t* payload, const tkv_amq_segment& sg, int part)
@@ -322,9 +396,11 @@ __device__ inline void write_page_header(uint8_t* out, const tkv_amq_segment& sg
 // v_add_co per load.  The lane offset has to be defined in the loop body as well (an empty asm on
 // the loop-carried variable, no instruction): instruction selection works per basic block and
 // sees the 32-bit offset's zero-extension only there; hoisted, it costs a v_lshl_add_u64 per load.
-// These asms, the one in bloom_insert and the leaf loops' sched_barrier hold an instruction form
-// no test sees: after a compiler update rerun the check in profiles/leaf_loop/README.md
-// ("After a ROCm update"; tools/isa_loops.py: 972 / 1,096 and 618 / 696 v_* per full-chunk loop).
+// These asms, the ones in bloom_insert (the opaque block, the two v_bfi_b32 of the strided image)
+// and the leaf loops' sched_barrier hold an instruction form no test sees: after a compiler update
+// rerun the check in profiles/lds_stride/README.md ("After a ROCm update"; tools/isa_loops.py:
+// 952 / 1,072 and 608 / 684 v_* per full-chunk loop; 972 / 1,096 and 618 / 696 before the strided
+// image, profiles/leaf_loop/README.md).
 TKV_INLINE uint64_t sgpr_addr(const uint8_t* base)
 {
   uint64_t a = reinterpret_cast<uint64_t>(base);
@@ -362,7 +438,7 @@ __device__ inline void bloom_keys16_lds(const uint4* __restrict__ kp, uint32_t n
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      bloom_insert<K>(s_bits, nb, k, Bloom16(kv[u]));
+      bloom_insert<K, false, true>(s_bits, nb, k, Bloom16(kv[u]));
       __builtin_amdgcn_sched_barrier(0);  // one key at a time: interleaved, four keys take 93 VGPRs
     }
   }
@@ -376,7 +452,7 @@ __device__ inline void bloom_keys16_lds(const uint4* __restrict__ kp, uint32_t n
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t i = base + u * NT + tid;
-      if (i < n) bloom_insert<K>(s_bits, nb, k, Bloom16(kv[u]));
+      if (i < n) bloom_insert<K, false, true>(s_bits, nb, k, Bloom16(kv[u]));
     }
   }
 }
@@ -404,7 +480,7 @@ __device__ inline void bloom_keysL_lds(const uint64_t* __restrict__ kp, uint32_t
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      bloom_insert<K>(s_bits, nb, k, BloomFixed<L>(lanes[u]));
+      bloom_insert<K, false, true>(s_bits, nb, k, BloomFixed<L>(lanes[u]));
       __builtin_amdgcn_sched_barrier(0);  // one key at a time, as in bloom_keys16_lds
     }
   }
@@ -419,13 +495,13 @@ __device__ inline void bloom_keysL_lds(const uint64_t* __restrict__ kp, uint32_t
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (base + u * NT + tid < n) {
-        bloom_insert<K>(s_bits, nb, k, BloomFixed<L>(lanes[u]));
+        bloom_insert<K, false, true>(s_bits, nb, k, BloomFixed<L>(lanes[u]));
       }
     }
   }
 }
 
-// Keys [kb, ke) of one leaf into its LDS image s_bits (NT threads).
+// Keys [kb, ke) of one leaf into its strided LDS image s_bits (NT threads).
 template <int MODE, uint32_t NT>
 __device__ inline void bloom_leaf_image(const uint8_t* __restrict__ keys,
                                         const uint64_t* __restrict__ offs, uint32_t stride,
@@ -585,7 +661,7 @@ __device__ inline void var_key_insert(uint32_t* s_bits, uint32_t nb, uint32_t k,
     uint64_t l[3];
     uint32_t t4, tb;
     key_win_parts(v.w, v.len, l, t4, tb);
-    bloom_insert<K>(s_bits, nb, k, BloomShort(v.len, l, t4, tb));
+    bloom_insert<K, false, true>(s_bits, nb, k, BloomShort(v.len, l, t4, tb));
   } else {
     bloom_insert_any<K, kKeyVar>(s_bits, nb, k, v.p, v.len);
   }
@@ -672,16 +748,17 @@ __global__ __launch_bounds__(NT) void bloom_build_lds(const uint8_t* __restrict_
                                                        const tkv_amq_segment* __restrict__ segs,
                                                        uint8_t* __restrict__ out, uint32_t var_sort)
 {
-  extern __shared__ uint32_t s_lds[];
+  // (region-aligned, as the strided image needs its base; the sort's scratch keeps it so)
+  extern __shared__ __attribute__((aligned(kStrideRegionBytes))) uint32_t s_lds[];
+  static_assert(4 * kVarAuxWords<NT> % kStrideRegionBytes == 0, "the image behind the scratch must stay region-aligned");
   const bool sorted = MODE == kKeyVar && var_sort;
   uint32_t* s_bits = s_lds + (sorted ? kVarAuxWords<NT> : 0u);
   const tkv_amq_segment sg = segs[blockIdx.x];
   const uint32_t n = sg.n_keys, nb = sg.n_blocks, k = sg.hash_count;
   if (k == 0) return;  // bits_per_key == 0: no filter (filter_builder.hpp:115-117)
   const uint32_t tid = threadIdx.x;
-  const uint32_t nwords = nb * 16;
 
-  for (uint32_t w = tid; w < nwords; w += NT) s_bits[w] = 0;
+  lds_stride_zero<NT>(s_bits, nb);
   __syncthreads();
   if constexpr (MODE == kKeyVar) {
     if (sorted) {
@@ -702,9 +779,7 @@ __global__ __launch_bounds__(NT) void bloom_build_lds(const uint8_t* __restrict_
   uint8_t* payload = out + sg.out_offset;
   if (tid < 4) write_bloom_header(payload, sg, tid);
   else if (tid < 8) write_page_header(out, sg, kLayoutBloom, tid - 4);
-  uint4* dst = reinterpret_cast<uint4*>(payload + kBloomHeader);
-  const uint4* src = reinterpret_cast<const uint4*>(s_bits);
-  for (uint32_t q = tid; q < nb * 4; q += NT) dst[q] = src[q];
+  lds_stride_write_out<NT>(s_bits, nb, reinterpret_cast<uint4*>(payload + kBloomHeader));
 }
 
 // Batches too small to fill the chip with one workgroup per leaf (one leaf per call, or a
@@ -727,21 +802,19 @@ __global__ __launch_bounds__(kSplitThreads) void bloom_build_split(
     uint64_t img_stride)
 {
   constexpr uint32_t NT = kSplitThreads;
-  extern __shared__ uint32_t s_bits[];
+  extern __shared__ __attribute__((aligned(kStrideRegionBytes))) uint32_t s_bits[];  // (strided)
   const uint32_t seg = blockIdx.x / parts, part = blockIdx.x - seg * parts;
   const tkv_amq_segment sg = segs[seg];
   const uint32_t n = sg.n_keys, nb = sg.n_blocks;
   if (sg.hash_count == 0) return;  // no filter
-  const uint32_t tid = threadIdx.x;
-  for (uint32_t w = tid; w < nb * 16; w += NT) s_bits[w] = 0;
+  lds_stride_zero<NT>(s_bits, nb);
   __syncthreads();
   const uint32_t chunk = (n + parts - 1) / parts;
   const uint32_t kb = min(n, part * chunk), ke = min(n, kb + chunk);
   bloom_leaf_image<MODE, NT>(keys, offs, stride, sg, kb, ke, s_bits);
   __syncthreads();
-  const uint4* img = reinterpret_cast<const uint4*>(s_bits);
-  uint4* dst = reinterpret_cast<uint4*>(ws + (uint64_t)blockIdx.x * img_stride);
-  for (uint32_t q = tid; q < nb * 4; q += NT) dst[q] = img[q];
+  // (the workspace image is canonical: bloom_split_merge reads it as it always did)
+  lds_stride_write_out<NT>(s_bits, nb, reinterpret_cast<uint4*>(ws + (uint64_t)blockIdx.x * img_stride));
 }
 
 // one thread per 16-byte word of a leaf's image, kMergeThreads words per workgroup: all the
@@ -871,17 +944,18 @@ __device__ inline void win_insert(const uint8_t* __restrict__ keys, const uint64
                                   const WinItem<MODE>& it, uint32_t* s_bits)
 {
   const uint32_t loc = it.d[WinItem<MODE>::N - 1];
-  uint32_t* blk = s_bits + 16 * (loc & 0xfffu);
-  lds_set_bit(blk, loc >> 12);
+  // (loc's block is local to the window: the strided image's regions count from the window's first block)
+  const uint32_t blk = lds_stride_key(lds_addr(s_bits), loc & 0xfffu);
+  lds_set_bit_strided(blk, loc >> 12);
   if constexpr (MODE == kKey16) {
     Bloom16 x;
     x.rk1 = mk64(it.d[0], it.d[1]);
     x.k2 = mk64(it.d[2], it.d[3]);
     if constexpr (K != 0) {
 #pragma unroll
-      for (uint32_t j = 1; j < (uint32_t)K; ++j) lds_set_bit(blk, x.bit(j));
+      for (uint32_t j = 1; j < (uint32_t)K; ++j) lds_set_bit_strided(blk, x.bit(j));
     } else {
-      for (uint32_t j = 1; j < k; ++j) lds_set_bit(blk, x.bit(j));
+      for (uint32_t j = 1; j < k; ++j) lds_set_bit_strided(blk, x.bit(j));
     }
   } else if constexpr (MODE == kKey24) {
     BloomFixed<24> x;
@@ -890,9 +964,9 @@ __device__ inline void win_insert(const uint8_t* __restrict__ keys, const uint64
     x.k[1] = mk64(it.d[4], it.d[5]);
     if constexpr (K != 0) {
 #pragma unroll
-      for (uint32_t j = 1; j < (uint32_t)K; ++j) lds_set_bit(blk, x.bit(j));
+      for (uint32_t j = 1; j < (uint32_t)K; ++j) lds_set_bit_strided(blk, x.bit(j));
     } else {
-      for (uint32_t j = 1; j < k; ++j) lds_set_bit(blk, x.bit(j));
+      for (uint32_t j = 1; j < k; ++j) lds_set_bit_strided(blk, x.bit(j));
     }
   } else {
     uint32_t len;
@@ -900,10 +974,10 @@ __device__ inline void win_insert(const uint8_t* __restrict__ keys, const uint64
     const uint32_t kk = K != 0 ? (uint32_t)K : k;
     if (len < 32) {
       const BloomShort x(p, len);
-      for (uint32_t j = 1; j < kk; ++j) lds_set_bit(blk, x.bit(j));
+      for (uint32_t j = 1; j < kk; ++j) lds_set_bit_strided(blk, x.bit(j));
     } else {
       const BloomLong x{p, len};
-      for (uint32_t j = 1; j < kk; ++j) lds_set_bit(blk, x.bit(j));
+      for (uint32_t j = 1; j < kk; ++j) lds_set_bit_strided(blk, x.bit(j));
     }
   }
 }
@@ -981,7 +1055,8 @@ __global__ __launch_bounds__(kWinThreads) void bloom_build_window(
     const tkv_amq_segment* __restrict__ segs, uint32_t n_win, uint32_t win_blocks, uint32_t parts,
     uint8_t* __restrict__ ws, uint64_t img_stride, uint8_t* __restrict__ out)
 {
-  extern __shared__ uint32_t s_bits[];
+  // (strided, and local to the window: block wb of the leaf is the image's block 0)
+  extern __shared__ __attribute__((aligned(kStrideRegionBytes))) uint32_t s_bits[];
   const uint32_t per_seg = n_win * parts;
   const uint32_t seg = blockIdx.x / per_seg, r = blockIdx.x - seg * per_seg;
   const uint32_t w = r / parts, part = r - w * parts;
@@ -991,7 +1066,7 @@ __global__ __launch_bounds__(kWinThreads) void bloom_build_window(
   if (k == 0 || wb >= nb) return;  // no filter, or a window past this leaf's image
   const uint32_t wn = min(win_blocks, nb - wb);
   const uint32_t tid = threadIdx.x;
-  for (uint32_t q = tid; q < wn * 16; q += kWinThreads) s_bits[q] = 0;
+  lds_stride_zero<kWinThreads>(s_bits, wn);
   __syncthreads();
   const uint32_t chunk = (n + parts - 1) / parts;
   const uint32_t kb = min(n, part * chunk), ke = min(n, kb + chunk);
@@ -1014,9 +1089,7 @@ __global__ __launch_bounds__(kWinThreads) void bloom_build_window(
   } else {
     dst8 = ws + (uint64_t)(seg * parts + part) * img_stride + 64ull * wb;
   }
-  uint4* dst = reinterpret_cast<uint4*>(dst8);
-  const uint4* src = reinterpret_cast<const uint4*>(s_bits);
-  for (uint32_t q = tid; q < wn * 4; q += kWinThreads) dst[q] = src[q];
+  lds_stride_write_out<kWinThreads>(s_bits, wn, reinterpret_cast<uint4*>(dst8));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -5335,6 +5408,13 @@ constexpr uint32_t kBloomLdsBudget = 64 * 1024;  // dynamic LDS a launch gets wi
 // atomics.
 constexpr uint32_t kBloomLeafLdsBudget = 160 * 1024;
 constexpr uint32_t kBloomWideLds = 32 * 1024;
+// The dynamic LDS of a leaf, split or window launch: the strided image of its largest leaf (or
+// window), whole 512-byte regions.  Every routing threshold compares the canonical 64 bytes a
+// block and is a multiple of a region, so an image that passes one fits rounded up as well.
+inline size_t bloom_image_lds(uint64_t blocks) { return (size_t)lds_stride_bytes64(blocks); }
+static_assert(kBloomLeafLdsBudget % kStrideRegionBytes == 0 && kBloomWideLds % kStrideRegionBytes == 0 &&
+                  kBloomLdsBudget % kStrideRegionBytes == 0,
+              "a rounded-up image must fit where the canonical one does");
 // The LDS build runs one workgroup per leaf, so a batch of a few leaves (the per-leaf call
 // site, or a small LeafBatcher batch) keeps a few CUs busy for the whole leaf.  Below this many
 // leaves the keys are spread over n_keys/256 workgroups that set bits with device atomics.
@@ -6204,7 +6284,7 @@ inline void launch_bloom_split(const BuildArgs& b, const BloomPlan& p)
 {
   with_build_key_mode(b.bmode, [&](auto M) {
     launch_lds_cap<&bloom_build_split<decltype(M)::value>>(
-        kBloomLeafLdsBudget, dim3(b.n_segs * p.parts), dim3(kSplitThreads), 64ull * b.max_blocks, b.s, b.keys, b.offs,
+        kBloomLeafLdsBudget, dim3(b.n_segs * p.parts), dim3(kSplitThreads), bloom_image_lds(b.max_blocks), b.s, b.keys, b.offs,
         b.stride, b.d_segs, p.parts, static_cast<uint8_t*>(b.d_ws), 64ull * b.max_blocks);
   });
   launch_split_merge(b, p.parts);
@@ -6214,7 +6294,7 @@ inline void launch_bloom_window(const BuildArgs& b, const BloomPlan& p)
 {
   with_build_key_mode(b.bmode, [&](auto M) {
     launch_lds_cap<&bloom_build_window<decltype(M)::value>>(
-        kBloomLeafLdsBudget, dim3(b.n_segs * p.windows * p.parts), dim3(kWinThreads), 64ull * p.window_blocks, b.s,
+        kBloomLeafLdsBudget, dim3(b.n_segs * p.windows * p.parts), dim3(kWinThreads), bloom_image_lds(p.window_blocks), b.s,
         b.keys, b.offs, b.stride, b.d_segs, p.windows, p.window_blocks, p.parts, static_cast<uint8_t*>(b.d_ws),
         64ull * b.max_blocks, b.d_out);
   });
@@ -6611,8 +6691,8 @@ static int build_batch(int kind, const uint8_t* keys, const uint64_t* offs, uint
       case BloomRoute::Split: launch_bloom_split(b, p); break;
       case BloomRoute::Window: launch_bloom_window(b, p); break;
       case BloomRoute::Lds:
-        if (p.threads == 1024) launch_bloom_lds<1024>(b.bmode, n_segs, 64ull * max_blocks, s, keys, offs, stride, d_segs, d_out);
-        else launch_bloom_lds<256>(b.bmode, n_segs, 64ull * max_blocks, s, keys, offs, stride, d_segs, d_out);
+        if (p.threads == 1024) launch_bloom_lds<1024>(b.bmode, n_segs, bloom_image_lds(max_blocks), s, keys, offs, stride, d_segs, d_out);
+        else launch_bloom_lds<256>(b.bmode, n_segs, bloom_image_lds(max_blocks), s, keys, offs, stride, d_segs, d_out);
         break;
       case BloomRoute::TiledKeys:
         launch_mono(p.mono, s, keys, b.bmode == kKey24 ? 24u : 16u, (uint32_t)sizing_keys, d_segs, ws, d_out);
