@@ -41,7 +41,8 @@ _keys = {}
 
 def batch_keys(oracle, kind, counts):
     """The batch's keys (sorted inside each leaf for VQF, whose build replays the leaf's order),
-    ~4,000 queries -- hits from every leaf and misses -- and the leaf each one asks."""
+    ~4,000 queries -- hits from every leaf and misses -- and the leaf each one asks (a batch of
+    thousands of leaves has more hits than that and no misses; its tests do not use the queries)."""
     key = (kind, tuple(counts))
     if key not in _keys:
         bounds = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
@@ -55,7 +56,7 @@ def batch_keys(oracle, kind, counts):
             hit_idx.append(int(bounds[s]) + rng.choice(c, take, replace=False) if take else np.zeros(0, np.int64))
             hit_seg.append(np.full(take, s))
         hit_idx, hit_seg = np.concatenate(hit_idx).astype(np.int64), np.concatenate(hit_seg)
-        n_miss = 4000 - len(hit_idx)
+        n_miss = max(4000 - len(hit_idx), 0)     # (a batch of thousands of leaves: hits only)
         q = np.concatenate([keys[hit_idx], oracle.gen_keys16(78, 0, n_miss)])
         qs = np.concatenate([hit_seg, rng.integers(0, len(counts), n_miss)]).astype(np.uint32)
         _keys[key] = (keys, bounds, q, qs)
@@ -270,6 +271,26 @@ def test_scan(oracle, amq, torch, kind, bpk, counts):
     fill = amq.filter_fill(plan, got)
     slots = 512.0 if kind == BLOOM else np.where(plan.segs["tag_bits"] == 8, 48.0, 28.0)
     assert np.allclose(fill, want["occupied"] / (plan.segs["n_blocks"] * slots), rtol=0, atol=1e-15)
+
+
+# More leaves than the 1,024 threads of the workgroup that turns the leaves' chunk counts into
+# their prefix (prefix_inclusive_u64, turtle_kv_amd/csrc/tkv_amq_scan.h): a thread's serial run is
+# 1, 2 and 3 elements, with idle threads at the end in the last two.
+@pytest.mark.parametrize("n_leaves", [1024, 1025, 2100])
+@pytest.mark.parametrize("kind,bpk", [(BLOOM, 10), (VQF, 12)])
+def test_scan_more_leaves_than_prefix_threads(oracle, amq, torch, kind, bpk, n_leaves):
+    counts = [1 + (37 * i) % 9 for i in range(n_leaves)]
+    plan, _, filt, ref = build(oracle, amq, torch, kind, bpk, counts, "offsets")
+    want = ref_stats(kind, ref, plan)
+    got = amq.scan_filters(plan, filt)
+    assert len(got) == n_leaves
+    for name in STAT_FIELDS:
+        assert np.array_equal(got[name], want[name]), (name, np.flatnonzero(got[name] != want[name])[:8])
+    assert not got["bad_blocks"].any() and got["occupied"].all()
+    if kind == BLOOM:
+        assert list(got["header_items"]) == counts
+    else:
+        assert np.array_equal(got["occupied"], got["header_items"])
 
 
 @pytest.mark.parametrize("bpk", [12, 22])

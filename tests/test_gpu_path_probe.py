@@ -10,8 +10,8 @@ pytestmark = pytest.mark.gpu
 COUNTS = [16384, 16384, 16384, 8448, 0, 5, 1, 9000]
 VQF_CAP = 32704
 VQF_SEED = 0x9D0924DC03E79A75
-# workgroup totals one pass of path_scan_totals covers (kPathScanSpan = 256 *
-# kPathScanPerThread, turtle_kv_amd/csrc/tkv_amq_kernels.hip), each the sum of 256 queries
+# workgroup totals one pass of scan_totals covers (kScanTotalsSpan = 256 *
+# kScanTotalsPerThread, turtle_kv_amd/csrc/tkv_amq_scan.h), each the sum of 256 queries
 SCAN_SPAN = 256 * 4
 QUERIES_PER_WG = 256
 SETTINGS = [(0, 10), (0, 12), (0, 16), (1, 12), (1, 22)]

@@ -427,6 +427,32 @@ def test_big_bloom_leaf(oracle, amq, torch, name, counts, shape):
     assert 0.3 * counts[0] < em[0] < 0.7 * counts[0]
 
 
+# More leaves than the 1,024 threads of the workgroup that turns the leaves' unit counts into
+# their prefix (prefix_inclusive_u64, turtle_kv_amd/csrc/tkv_amq_scan.h): a thread's serial run is
+# 1, 2 and 3 elements, with idle threads at the end in the last two.  A unit past the first
+# 1,024 leaves finds its own leaf through that prefix: the damage is reported on the damaged
+# leaves and nowhere else.
+@pytest.mark.parametrize("n_leaves", [1024, 1025, 2100])
+@pytest.mark.parametrize("kind,bpk,cap", [(BLOOM, 10, 0), (VQF, 12, 32704)])
+def test_more_leaves_than_prefix_threads(oracle, amq, torch, kind, bpk, cap, n_leaves):
+    counts = [1 + (37 * i) % 9 for i in range(n_leaves)]
+    hk, _ = host_keys(oracle, "k16", sum(counts))
+    kb = key_batch(amq, torch, "k16", hk, None)
+    plan, filt = build(amq, torch, kind, bpk, cap, counts, kb)
+    zero_m, none = np.zeros(n_leaves, np.uint32), np.full(n_leaves, U64, np.uint64)
+    for hint in HINTS:
+        got, total = run(amq, torch, plan, filt, kb, hint=hint)
+        assert_result(got, total, zero_m, none, flags=0)
+    # the blocks of leaf 1,024 (where it exists) and of the last leaf zeroed
+    damaged = sorted({n_leaves - 1} | ({1024} if n_leaves > 1024 else set()))
+    bad = filt.cpu().numpy().copy()
+    for s in damaged:
+        o = int(plan.segs[s]["out_offset"]) + (64 if kind == BLOOM else 80)
+        bad[o:o + 64 * int(plan.segs[s]["n_blocks"])] = 0
+    em, _ = check_damaged16(oracle, amq, torch, plan, dev(torch, bad), hk, kb, damaged=damaged)
+    assert list(np.flatnonzero(em)) == damaged
+
+
 # ---------------------------------------------------------------------------------------
 # 6. determinism and graph capture
 # ---------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "tkv_amq.h"
+#include "tkv_amq_key_order.h"  // be64, key_compare and the unaligned loads
 
 namespace tkv {
 
@@ -218,48 +219,6 @@ __host__ __device__ constexpr inline uint64_t xxh16_rhinit(uint64_t seed)
   return rotl64(seed + kP5 + 16, 27);
 }
 
-// Unaligned global loads: gfx950 (HSA, unaligned access mode) serves a dwordx2 / dword load
-// at any byte address; memcpy from a byte pointer compiles to exactly that
-// (tools/probe/unaligned_load.hip checks every byte offset on the device).
-__device__ inline uint64_t ld64_unaligned(const uint8_t* p)
-{
-  uint64_t v;
-  __builtin_memcpy(&v, p, 8);
-  return v;
-}
-
-__device__ inline uint32_t ld32_unaligned(const uint8_t* p)
-{
-  uint32_t v;
-  __builtin_memcpy(&v, p, 4);
-  return v;
-}
-
-// ---- key order, shared by the leaf search (tkv_amq_find.hip) and the tree walk
-// (tkv_amq_walk.hip): keys as big-endian words, so an unsigned integer compare is memcmp ----
-__device__ inline uint64_t be64(uint32_t lo, uint32_t hi) { return __builtin_bswap64(mk64(lo, hi)); }
-
-// memcmp order, then the shorter key first (std::string_view's): < 0, 0, > 0 for k <, ==, > q
-__device__ inline int key_compare(const uint8_t* k, uint32_t klen, const uint8_t* q, uint32_t qlen)
-{
-  const uint32_t n = klen < qlen ? klen : qlen;
-  uint32_t o = 0;
-  for (; o + 8 <= n; o += 8) {
-    const uint64_t x = ld64_unaligned(k + o), y = ld64_unaligned(q + o);
-    if (x != y) return __builtin_bswap64(x) < __builtin_bswap64(y) ? -1 : 1;
-  }
-  if (o + 4 <= n) {
-    const uint32_t x = ld32_unaligned(k + o), y = ld32_unaligned(q + o);
-    if (x != y) return __builtin_bswap32(x) < __builtin_bswap32(y) ? -1 : 1;
-    o += 4;
-  }
-  for (; o < n; ++o) {
-    const uint32_t x = k[o], y = q[o];
-    if (x != y) return x < y ? -1 : 1;
-  }
-  return klen < qlen ? -1 : (klen > qlen ? 1 : 0);
-}
-
 // Any key shorter than 32 bytes (XXH64's short-input path), any alignment: the 8-byte lane
 // rounds and the 4-byte / 1-byte tail products do not depend on the seed, so they are
 // computed once per key; per seed only the chained rotate-multiply steps and the avalanche
@@ -432,6 +391,13 @@ __device__ inline uint32_t wave_sum(uint32_t v)
   return v;
 }
 
+__device__ inline uint32_t wave_max32(uint32_t v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o, 64));
+  return v;
+}
+
 // ---- reject_page's classes, shared by the probes (tkv_amq_kernels.hip) and the leaf search
 // (tkv_amq_find.hip) ----
 // Probe-side view of a segment: the first 16 bytes of tkv_amq_segment in one load.
@@ -458,6 +424,9 @@ __device__ inline ProbeDesc load_probe_desc(const tkv_amq_segment* segs, uint32_
 }
 
 enum ProbeClass : uint32_t { kNoFilter = 0, kIdMismatch = 1, kChecked = 2 };
+
+// byte offset of src_page_id in a filter's payload: PackedBloomFilterPage @16, PackedVqfFilter @8
+__host__ __device__ constexpr inline uint32_t src_page_id_offset(int kind) { return kind == TKV_AMQ_BLOOM ? 16u : 8u; }
 
 // filter header's src_page_id (PackedBloomFilterPage / PackedVqfFilter) vs the leaf the query
 // asks about (reject_page, tree/key_query.hpp:205-212,227-232): the filter bytes decide, as in

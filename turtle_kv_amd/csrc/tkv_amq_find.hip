@@ -32,10 +32,6 @@ constexpr uint32_t kFindThreads = 256;
 // workgroups), so the counters take at most 16,384 waves' atomics each, spread over the run
 constexpr uint32_t kFindMaxGrid = 4096;
 
-// kFind16: both sides fixed 16-byte keys, 16-byte aligned; kFind24: both fixed 24-byte keys,
-// 8-byte aligned; kFindAny: everything else (other strides, offsets on either side, misaligned)
-enum FindMode : int { kFind16 = 0, kFind24 = 1, kFindAny = 2 };
-
 struct FindArgs {
   const uint8_t* filters;
   const tkv_amq_segment* segs;
@@ -63,112 +59,6 @@ struct FindArgs {
   tkv_amq_find_counts* counts;
 };
 
-// The query of one lane, and its comparison with leaf key `i`.
-template <int MODE>
-struct FindQuery;
-
-template <>
-struct FindQuery<kFind16> {
-  uint64_t w0, w1;
-  __device__ inline FindQuery(const FindArgs& a, uint64_t i)
-  {
-    const uint4 v = *reinterpret_cast<const uint4*>(a.q + 16 * i);
-    w0 = be64(v.x, v.y);
-    w1 = be64(v.z, v.w);
-  }
-  // one global_load_dwordx4, two u64 compares
-  __device__ inline void load(const FindArgs& a, uint64_t i, uint64_t& k0, uint64_t& k1) const
-  {
-    const uint4 v = *reinterpret_cast<const uint4*>(a.keys + 16 * i);
-    k0 = be64(v.x, v.y);
-    k1 = be64(v.z, v.w);
-  }
-  __device__ inline bool less(const FindArgs& a, uint64_t i) const
-  {
-    uint64_t k0, k1;
-    load(a, i, k0, k1);
-    return k0 < w0 || (k0 == w0 && k1 < w1);
-  }
-  __device__ inline bool equal(const FindArgs& a, uint64_t i) const
-  {
-    uint64_t k0, k1;
-    load(a, i, k0, k1);
-    return k0 == w0 && k1 == w1;
-  }
-};
-
-template <>
-struct FindQuery<kFind24> {
-  uint64_t w0, w1, w2;
-  __device__ inline FindQuery(const FindArgs& a, uint64_t i)
-  {
-    const uint64_t* p = reinterpret_cast<const uint64_t*>(a.q + 24 * i);
-    w0 = __builtin_bswap64(p[0]);
-    w1 = __builtin_bswap64(p[1]);
-    w2 = __builtin_bswap64(p[2]);
-  }
-  __device__ inline bool less(const FindArgs& a, uint64_t i) const
-  {
-    const uint64_t* p = reinterpret_cast<const uint64_t*>(a.keys + 24 * i);
-    const uint64_t k0 = __builtin_bswap64(p[0]), k1 = __builtin_bswap64(p[1]), k2 = __builtin_bswap64(p[2]);
-    return k0 < w0 || (k0 == w0 && (k1 < w1 || (k1 == w1 && k2 < w2)));
-  }
-  __device__ inline bool equal(const FindArgs& a, uint64_t i) const
-  {
-    const uint64_t* p = reinterpret_cast<const uint64_t*>(a.keys + 24 * i);
-    return __builtin_bswap64(p[0]) == w0 && __builtin_bswap64(p[1]) == w1 && __builtin_bswap64(p[2]) == w2;
-  }
-};
-
-template <>
-struct FindQuery<kFindAny> {
-  const uint8_t* p;
-  uint32_t len;
-  __device__ inline FindQuery(const FindArgs& a, uint64_t i)
-  {
-    if (a.qoffs) {
-      const uint64_t b = a.qoffs[i];
-      p = a.q + b;
-      len = (uint32_t)(a.qoffs[i + 1] - b);
-    } else {
-      p = a.q + i * a.qstride;
-      len = a.qstride;
-    }
-  }
-  __device__ inline int compare(const FindArgs& a, uint64_t i) const
-  {
-    const uint8_t* k;
-    uint32_t klen;
-    if (a.koffs) {
-      const uint64_t b = a.koffs[i];
-      k = a.keys + b;
-      klen = (uint32_t)(a.koffs[i + 1] - b);
-    } else {
-      k = a.keys + i * a.kstride;
-      klen = a.kstride;
-    }
-    return key_compare(k, klen, p, len);
-  }
-  __device__ inline bool less(const FindArgs& a, uint64_t i) const { return compare(a, i) < 0; }
-  __device__ inline bool equal(const FindArgs& a, uint64_t i) const { return compare(a, i) == 0; }
-};
-
-// keys [b, e) of leaf `leaf` (< n_segs): both ends clamped to n_keys, end < begin reads as empty
-__device__ inline void leaf_range(const FindArgs& a, uint32_t leaf, uint64_t& b, uint64_t& e)
-{
-  if (a.key_begin) {
-    b = a.key_begin[leaf];
-    e = a.key_begin[leaf + 1];
-  } else {
-    b = a.segs[leaf].key_begin;
-    e = b + a.segs[leaf].n_keys;
-    if (e < b) e = ~0ull;
-  }
-  b = b < a.n_keys ? b : a.n_keys;
-  e = e < a.n_keys ? e : a.n_keys;
-  if (e < b) e = b;
-}
-
 // reject_page's class of (candidate at `pos`, leaf), as the probes compute it: is it kChecked?
 __device__ inline bool find_checked(const FindArgs& a, uint32_t leaf, uint32_t pos)
 {
@@ -194,7 +84,8 @@ __global__ __launch_bounds__(kFindThreads) void find_keys_kernel(FindArgs a)
     uint64_t r_key = ~0ull;
     uint32_t r_leaf = ~0u, r_cand = ~0u;
     if (cb < ce) {  // (a query without candidates does not load its key)
-      const FindQuery<MODE> q(a, i);
+      const KeyArray ks{a.keys, a.koffs, a.kstride};
+      const OrderedQuery<MODE> q(KeyArray{a.q, a.qoffs, a.qstride}, i);
       bool done = false;
       for (uint32_t pos = cb; pos < ce; ++pos) {
         uint32_t st = TKV_AMQ_CAND_NOT_SEARCHED;
@@ -205,16 +96,10 @@ __global__ __launch_bounds__(kFindThreads) void find_keys_kernel(FindArgs a)
             ++n_unsearchable;
           } else {
             uint64_t b, e;
-            leaf_range(a, leaf, b, e);
-            // branch-free lower bound: lanes with leaves of equal size take the same trip count
-            uint64_t len = e - b;
-            while (len > 1) {
-              const uint64_t half = len >> 1;
-              b += q.less(a, b + half - 1) ? half : 0;
-              len -= half;
-            }
-            if (len == 1) b += q.less(a, b) ? 1 : 0;
-            const bool hit = b < e && q.equal(a, b);
+            leaf_key_range(a.key_begin, a.segs, leaf, a.n_keys, b, e);
+            // the lower bound: lanes with leaves of equal size take the same trip count
+            b = bound(b, e - b, [&](uint64_t k) { return q.less(ks, k); });
+            const bool hit = b < e && q.equal(ks, b);
             ++n_search;
             if (hit) {
               st = TKV_AMQ_CAND_FOUND;
@@ -289,7 +174,7 @@ int tkv_amq_find_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment*
   a.filters = d_filters;
   a.segs = d_segs;
   a.n_segs = n_segs;
-  a.id_off = kind == TKV_AMQ_BLOOM ? 16u : 8u;
+  a.id_off = src_page_id_offset(kind);
   a.kind = kind;
   a.flags = flags;
   a.q = queries;
@@ -310,18 +195,14 @@ int tkv_amq_find_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment*
   a.page_ids = opts ? opts->d_query_page_id : nullptr;
   a.metrics = opts ? opts->d_metrics : nullptr;
   a.counts = d_counts;
-  // the fast modes, chosen as the build chooses them
-  const bool fixed = !query_offsets && !leaf_key_offsets && query_stride == leaf_key_stride;
-  const uintptr_t both = reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(leaf_keys);
-  const int mode = fixed && query_stride == 16 && !(both & 15) ? kFind16
-                   : fixed && query_stride == 24 && !(both & 7) ? kFind24
-                                                                : kFindAny;
+  const int mode = key_order_mode(KeyArray{queries, query_offsets, query_stride},
+                                  KeyArray{leaf_keys, leaf_key_offsets, leaf_key_stride});
   const uint64_t wgs = (n_queries + kFindThreads - 1) / kFindThreads;
   const dim3 grid((uint32_t)(wgs < kFindMaxGrid ? wgs : kFindMaxGrid)), block(kFindThreads);
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mode == kFind16) hipLaunchKernelGGL(find_keys_kernel<kFind16>, grid, block, 0, s, a);
-  else if (mode == kFind24) hipLaunchKernelGGL(find_keys_kernel<kFind24>, grid, block, 0, s, a);
-  else hipLaunchKernelGGL(find_keys_kernel<kFindAny>, grid, block, 0, s, a);
+  if (mode == kOrder16) hipLaunchKernelGGL(find_keys_kernel<kOrder16>, grid, block, 0, s, a);
+  else if (mode == kOrder24) hipLaunchKernelGGL(find_keys_kernel<kOrder24>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(find_keys_kernel<kOrderAny>, grid, block, 0, s, a);
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
 

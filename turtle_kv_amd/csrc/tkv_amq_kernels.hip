@@ -43,6 +43,7 @@
 #include "tkv_amq.h"
 #include "tkv_amq_device.h"
 #include "tkv_amq_lds_stride.h"
+#include "tkv_amq_scan.h"
 
 // The one diagnostic build option (TKV_DIAG_RING: per-step timestamps of vqf_ring_place's
 // decider, read by tools/ring_diag.py) is for experiment libraries only; the shipped library
@@ -1498,30 +1499,11 @@ __global__ __launch_bounds__(NT) void route_keys(const uint8_t* __restrict__ key
   }
 }
 
-// exclusive scan of 256 per-thread values in a 256-thread block; returns this thread's prefix
-// and sets *total
-__device__ inline uint32_t block_exclusive_scan256(uint32_t v, uint32_t* s, uint32_t* total)
-{
-  const uint32_t tid = threadIdx.x;
-  s[tid] = v;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1) {
-    const uint32_t a = tid >= d ? s[tid - d] : 0u;
-    __syncthreads();
-    s[tid] += a;
-    __syncthreads();
-  }
-  *total = s[255];
-  const uint32_t r = s[tid] - v;
-  __syncthreads();
-  return r;
-}
-
 // One workgroup per part: H[w][p] <- sum of H[w'][p] over w' < w; totals[p] <- column sum.
 __global__ __launch_bounds__(256) void route_scan_cols(uint32_t* __restrict__ ws, uint32_t P,
                                                        uint32_t n_parts)
 {
-  __shared__ uint32_t s[256];
+  __shared__ uint32_t s[4];
   const uint32_t t = blockIdx.x, tid = threadIdx.x;
   constexpr uint32_t R = kRouteMaxWgs / 256;  // rows per thread
   uint32_t v[R];
@@ -1533,7 +1515,7 @@ __global__ __launch_bounds__(256) void route_scan_cols(uint32_t* __restrict__ ws
     sum += v[r];
   }
   uint32_t total;
-  uint32_t run = block_exclusive_scan256(sum, s, &total);
+  uint32_t run = block_exclusive_scan<uint32_t>(sum, s, &total);
 #pragma unroll
   for (uint32_t r = 0; r < R; ++r) {
     const uint32_t w = tid * R + r;
@@ -1547,7 +1529,7 @@ __global__ __launch_bounds__(256) void route_scan_cols(uint32_t* __restrict__ ws
 __global__ __launch_bounds__(256) void route_scan_parts(uint32_t* __restrict__ ws, uint32_t P,
                                                         uint32_t n_parts)
 {
-  __shared__ uint32_t s[256];
+  __shared__ uint32_t s[4];
   const uint32_t* tot = ws + (uint64_t)P * n_parts;
   uint32_t* base = ws + (uint64_t)P * n_parts + n_parts;
   const uint32_t tid = threadIdx.x;
@@ -1556,7 +1538,7 @@ __global__ __launch_bounds__(256) void route_scan_parts(uint32_t* __restrict__ w
   uint32_t sum = 0;
   for (uint32_t t = t0; t < t1; ++t) sum += tot[t];
   uint32_t total;
-  uint32_t run = block_exclusive_scan256(sum, s, &total);
+  uint32_t run = block_exclusive_scan<uint32_t>(sum, s, &total);
   for (uint32_t t = t0; t < t1; ++t) {
     base[t] = run;
     run += tot[t];
@@ -2712,7 +2694,7 @@ __device__ inline uint32_t bloom_probe_item(const uint8_t* __restrict__ filters,
     // hash_count 0: no filter page => reject_page returns kUnknown => cannot reject
     uint32_t cls = d.hash_count == 0 ? kNoFilter : kChecked;
     if constexpr (kOpts) {
-      if (cls == kChecked && !page_id_matches(filters + d.out_offset, 16, page_ids, i)) cls = kIdMismatch;
+      if (cls == kChecked && !page_id_matches(filters + d.out_offset, src_page_id_offset(TKV_AMQ_BLOOM), page_ids, i)) cls = kIdMismatch;
     }
     if (!kOpts || cls == kChecked) {
       if (d.hash_count == 7) ok = probe_block16<7>(x, h0, blk, slot);
@@ -2723,7 +2705,7 @@ __device__ inline uint32_t bloom_probe_item(const uint8_t* __restrict__ filters,
   } else {
     const ProbeDesc d = load_probe_desc(segs, sidx, n_segs);
     if (d.hash_count == 0) return 1u | (kNoFilter << 1);
-    if (!page_id_matches(filters + d.out_offset, 16, page_ids, i)) return 1u | (kIdMismatch << 1);
+    if (!page_id_matches(filters + d.out_offset, src_page_id_offset(TKV_AMQ_BLOOM), page_ids, i)) return 1u | (kIdMismatch << 1);
     const uint8_t* words = filters + d.out_offset + kBloomHeader;
     uint32_t len;
     const uint8_t* p = key_at<MODE>(q, qoffs, stride, i, len);
@@ -4736,7 +4718,7 @@ __device__ __attribute__((always_inline)) inline uint32_t vqf_probe_one(const ui
   if (d.tag_bits == 0) return 1u | (kNoFilter << 1);  // no filter: cannot reject
   const uint8_t* payload = filters + d.out_offset;
   if constexpr (kOpts) {
-    if (!page_id_matches(payload, 8, page_ids, i)) return 1u | (kIdMismatch << 1);
+    if (!page_id_matches(payload, src_page_id_offset(TKV_AMQ_VQF), page_ids, i)) return 1u | (kIdMismatch << 1);
   }
   const uint64_t mask = ~0ull << d.hash_val_shift;  // == PackedVqfFilter::hash_mask
   // dropped hash values are always "maybe" (:115-117)
@@ -4867,7 +4849,7 @@ __global__ __launch_bounds__(256) void bloom_probe_hashed(const uint8_t* __restr
     // a filter whose hash_count exceeds the cached k_max cannot be tested: cannot reject
     if (d.hash_count == 0 || d.hash_count > k_max) {
       r = 1u | (kNoFilter << 1);
-    } else if (kOpts && !page_id_matches(filters + d.out_offset, 16, opts.d_query_page_id, i)) {
+    } else if (kOpts && !page_id_matches(filters + d.out_offset, src_page_id_offset(TKV_AMQ_BLOOM), opts.d_query_page_id, i)) {
       r = 1u | (kIdMismatch << 1);
     } else {
       const uint16_t* bits = reinterpret_cast<const uint16_t*>(rec + 8);
@@ -4918,36 +4900,16 @@ __global__ __launch_bounds__(256) void vqf_hash_kernel(const uint8_t* __restrict
 //                       registers), tests the filter of every entry of its path, keeps the
 //                       answers of its first kPathMaskEntries entries as a bit mask (later
 //                       entries only as bytes), and counts its candidates; the workgroup scans
-//                       its 256 counts (path_block_scan256): cand_begin[i] <- prefix inside the workgroup,
+//                       its 256 counts (block_exclusive_scan): cand_begin[i] <- prefix inside the workgroup,
 //                       wg_total[w] <- the workgroup's sum
-//   path_scan_totals    one workgroup: exclusive scan of wg_total in passes of kPathScanSpan
+//   scan_totals<u32>    (tkv_amq_scan.h) one workgroup: exclusive scan of wg_total in passes of
+//                       kScanTotalsSpan; cand_begin[n_queries] <- the total, at most n_entries
+//                       (more candidates than entries: only paths that share entries)
 //   path_scatter        lane i again: cand_begin[i] += wg_total[w], then its candidates in path
 //                       order from the mask (answer bytes past kPathMaskEntries)
 // The mask is the query's own, so two paths that share entries (possible only when path_begin
 // is not monotone) cannot disturb each other's candidates.
-constexpr uint32_t kPathScanPerThread = 4;
-constexpr uint32_t kPathScanSpan = 256 * kPathScanPerThread;  // workgroup totals per scan pass
 constexpr uint32_t kPathMaskEntries = 32;
-
-// exclusive scan of 256 per-thread values: a shuffle scan inside each wave, the four wave sums
-// through LDS (two barriers, where block_exclusive_scan256 takes eighteen); s_w: 4 words
-__device__ inline uint32_t path_block_scan256(uint32_t v, uint32_t* s_w, uint32_t* total)
-{
-  const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t u = __shfl_up(inc, d, 64);
-    if (lane >= (uint32_t)d) inc += u;
-  }
-  if (lane == 63) s_w[wave] = inc;
-  __syncthreads();
-  const uint32_t w0 = s_w[0], w1 = s_w[1], w2 = s_w[2], w3 = s_w[3];
-  __syncthreads();  // (s_w is written again by the caller's next pass)
-  *total = w0 + w1 + w2 + w3;
-  const uint32_t wave_base = (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u);
-  return wave_base + inc - v;
-}
 
 struct PathArgs {
   const uint8_t* filters;
@@ -5017,7 +4979,7 @@ __device__ inline BloomEntry16 bloom_entry16_fetch(const uint8_t* __restrict__ f
   const ProbeDesc d = load_probe_desc(segs, leaf, n_segs);
   uint32_t cls = d.hash_count == 0 ? kNoFilter : kChecked;
   if constexpr (kOpts) {
-    if (cls == kChecked && !page_id_matches(filters + d.out_offset, 16, page_ids, ent)) cls = kIdMismatch;
+    if (cls == kChecked && !page_id_matches(filters + d.out_offset, src_page_id_offset(TKV_AMQ_BLOOM), page_ids, ent)) cls = kIdMismatch;
   }
   f.k_cls = d.hash_count | (cls << 16);
   f.blk = reinterpret_cast<const uint4*>(filters + d.out_offset + kBloomHeader +
@@ -5109,7 +5071,7 @@ __device__ inline uint32_t bloom_entry_test(const uint8_t* __restrict__ filters,
   const ProbeDesc d = load_probe_desc(segs, leaf, n_segs);
   if (d.hash_count == 0) return 1u | (kNoFilter << 1);
   if constexpr (kOpts) {
-    if (!page_id_matches(filters + d.out_offset, 16, page_ids, ent)) return 1u | (kIdMismatch << 1);
+    if (!page_id_matches(filters + d.out_offset, src_page_id_offset(TKV_AMQ_BLOOM), page_ids, ent)) return 1u | (kIdMismatch << 1);
   }
   const uint64_t* blk = reinterpret_cast<const uint64_t*>(filters + d.out_offset + kBloomHeader +
                                                           64 * bloom_block(h0, d.n_blocks));
@@ -5206,45 +5168,12 @@ __global__ __launch_bounds__(256, (MODE == kKey16 && !kOpts ? 8 : 4)) void path_
     }
     if (live) a.mask[i] = wk.mask;
     uint32_t total;
-    const uint32_t pre = path_block_scan256(wk.cnt, s_scan, &total);
+    const uint32_t pre = block_exclusive_scan<uint32_t>(wk.cnt, s_scan, &total);
     if (live) a.cand_begin[i] = pre;
     if (tid == 0) a.wg_total[w] = total;
     w += gridDim.x;
   } while (kOpts && w < a.n_wgs);
   if constexpr (kOpts) flush_tally(t, opts.d_metrics, opts.d_truth != nullptr);
-}
-
-// One workgroup: wg_total[w] <- sum of wg_total[w'] over w' < w, kPathScanSpan of them per
-// pass with the running base carried over; cand_begin[n_queries] <- the total.  (n_wgs == 0:
-// writes cand_begin[0] = 0, all an empty batch needs.)
-__global__ __launch_bounds__(256) void path_scan_totals(uint32_t* __restrict__ wg_total, uint32_t n_wgs,
-                                                        uint32_t* __restrict__ cand_begin,
-                                                        uint32_t n_queries, uint32_t n_entries)
-{
-  __shared__ uint32_t s[4];
-  const uint32_t tid = threadIdx.x;
-  uint32_t base = 0;
-  for (uint32_t p0 = 0; p0 < n_wgs; p0 += kPathScanSpan) {
-    uint32_t v[kPathScanPerThread];
-    uint32_t sum = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < kPathScanPerThread; ++r) {
-      const uint32_t w = p0 + tid * kPathScanPerThread + r;
-      v[r] = w < n_wgs ? wg_total[w] : 0u;
-      sum += v[r];
-    }
-    uint32_t total;
-    uint32_t run = base + path_block_scan256(sum, s, &total);
-#pragma unroll
-    for (uint32_t r = 0; r < kPathScanPerThread; ++r) {
-      const uint32_t w = p0 + tid * kPathScanPerThread + r;
-      if (w < n_wgs) wg_total[w] = run;
-      run += v[r];
-    }
-    base += total;
-  }
-  // (more candidates than entries: only paths that share entries; see path_scatter)
-  if (tid == 0) cand_begin[n_queries] = min(base, n_entries);
 }
 
 // Lane i writes query i's candidates in path order.  Positions at or past n_entries (the
@@ -7369,8 +7298,8 @@ int tkv_amq_path_probe(int kind, const uint8_t* d_filters, const tkv_amq_segment
   const hipStream_t s = as_stream(stream);
   if (n_queries == 0) {
     if (d_cand_begin) {
-      hipLaunchKernelGGL(path_scan_totals, dim3(1), dim3(256), 0, s, static_cast<uint32_t*>(nullptr), 0u,
-                         d_cand_begin, 0u, 0u);
+      hipLaunchKernelGGL(scan_totals<uint32_t>, dim3(1), dim3(256), 0, s, static_cast<uint32_t*>(nullptr), 0u,
+                         d_cand_begin, 0u, static_cast<uint64_t*>(nullptr));
       return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
     }
     return TKV_AMQ_OK;
@@ -7418,8 +7347,8 @@ int tkv_amq_path_probe(int kind, const uint8_t* d_filters, const tkv_amq_segment
         hipLaunchKernelGGL((path_probe_kernel<TKV_AMQ_VQF, MODE, kOpts>), grid, block, 0, s, a, o);
     });
   });
-  hipLaunchKernelGGL(path_scan_totals, dim3(1), dim3(256), 0, s, a.wg_total, a.n_wgs, d_cand_begin,
-                     a.n_queries, a.n_entries);
+  hipLaunchKernelGGL(scan_totals<uint32_t>, dim3(1), dim3(256), 0, s, a.wg_total, a.n_wgs,
+                     d_cand_begin + a.n_queries, a.n_entries, static_cast<uint64_t*>(nullptr));
   hipLaunchKernelGGL(path_scatter, dim3(a.n_wgs), block, 0, s, a);
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }

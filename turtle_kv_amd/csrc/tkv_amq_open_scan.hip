@@ -5,7 +5,7 @@
 //                        spec and writes the segment the probes address
 //                        with -- what KeyQuery::reject_page reads from a loaded filter page
 //                        (tree/key_query.hpp:149-247, vqf_filter_page_view.hpp:96-100).
-//   scan_init / scan_prefix / scan_blocks / scan_fold
+//   scan_init / prefix_inclusive_u64 (tkv_amq_scan.h) / scan_blocks / scan_fold
 //                        a read-only pass over every filter's blocks: the
 //                        blocks are cut into chunks of kScanChunkBlocks, a device-side prefix
 //                        over the segments' chunk counts lives in the workspace, and every
@@ -24,6 +24,7 @@
 
 #include "tkv_amq.h"
 #include "tkv_amq_device.h"
+#include "tkv_amq_scan.h"
 
 namespace tkv {
 namespace {
@@ -35,7 +36,6 @@ constexpr uint64_t kVqfBlocksMax = 1ull << 24;              // kVqfMaxBlocks of 
 constexpr uint32_t kScanThreads = 256;
 constexpr uint32_t kScanRows = 4;                                // 16-byte loads per lane per chunk
 constexpr uint32_t kScanChunkBlocks = kScanRows * kScanThreads / 4;  // 256 blocks = 16 KiB
-constexpr uint32_t kPrefixThreads = 1024;
 constexpr uint32_t kScanMaxGrid = 4096;  // scan_blocks' workgroups at most: one 32-byte slot each
 constexpr uint32_t kFoldThreads = 256;
 constexpr uint64_t kScanWsHeader = 16;
@@ -224,50 +224,9 @@ __global__ __launch_bounds__(256) void scan_init(int kind, const uint8_t* __rest
   pre[s + 1] = ((uint64_t)g.n_blocks + kScanChunkBlocks - 1) / kScanChunkBlocks;
 }
 
-// in-place inclusive scan of v[0 .. n) by one workgroup: a serial run per thread, the runs'
-// sums scanned over the wave with shuffles, the waves' totals through LDS
-__global__ __launch_bounds__(kPrefixThreads) void scan_prefix(uint64_t* __restrict__ v, uint32_t n)
-{
-  __shared__ uint64_t s_wave[kPrefixThreads / 64];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint64_t per = ((uint64_t)n + kPrefixThreads - 1) / kPrefixThreads;
-  const uint64_t b = per * tid < n ? per * tid : n;
-  const uint64_t e = b + per < n ? b + per : n;
-  uint64_t sum = 0;
-  for (uint64_t i = b; i < e; ++i) sum += v[i];
-  uint64_t inc = sum;  // inclusive over the wave
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t up = __shfl_up(inc, o, 64);
-    if ((int)lane >= o) inc += up;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  uint64_t run = inc - sum;
-  for (uint32_t w = 0; w < wave; ++w) run += s_wave[w];
-  for (uint64_t i = b; i < e; ++i) {
-    run += v[i];
-    v[i] = run;
-  }
-}
-
 struct ScanAcc {
   uint32_t occ = 0, full = 0, empty = 0, maxb = 0, bad = 0;
 };
-
-__device__ inline uint32_t wave_sum32(uint32_t v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ inline uint32_t wave_max32(uint32_t v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o, 64));
-  return v;
-}
 
 // Adds the workgroup's counts to one segment's stats: reduced over each wave with shuffles, over
 // the workgroup's waves through LDS, then one atomic per non-zero counter.  max_block takes its
@@ -276,8 +235,8 @@ __device__ inline uint32_t wave_max32(uint32_t v)
 // would otherwise queue two same-address atomics per workgroup.
 __device__ inline void scan_flush(ScanAcc& a, tkv_amq_filter_stats* st, uint32_t (*s_part)[5])
 {
-  const uint32_t v[5] = {wave_sum32(a.occ), wave_sum32(a.full), wave_sum32(a.empty), wave_max32(a.maxb),
-                         wave_sum32(a.bad)};
+  const uint32_t v[5] = {wave_sum(a.occ), wave_sum(a.full), wave_sum(a.empty), wave_max32(a.maxb),
+                         wave_sum(a.bad)};
   const uint32_t wave = threadIdx.x >> 6;
   __syncthreads();  // (the previous flush's readers are done with s_part)
   if (__lane_id() == 0) {
@@ -320,8 +279,8 @@ static_assert(sizeof(ScanSlot) == 32, "one 32-byte slot per workgroup");
 
 __device__ inline void scan_finish(ScanAcc& a, ScanSlot* slot, uint32_t seg, uint32_t (*s_part)[5])
 {
-  const uint32_t v[5] = {wave_sum32(a.occ), wave_sum32(a.full), wave_sum32(a.empty), wave_max32(a.maxb),
-                         wave_sum32(a.bad)};
+  const uint32_t v[5] = {wave_sum(a.occ), wave_sum(a.full), wave_sum(a.empty), wave_max32(a.maxb),
+                         wave_sum(a.bad)};
   const uint32_t wave = threadIdx.x >> 6;
   __syncthreads();
   if (__lane_id() == 0) {
@@ -641,7 +600,7 @@ int tkv_amq_scan_filters(int kind, const uint8_t* d_filters, const tkv_amq_segme
   uint64_t* pre = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(d_workspace) + kScanWsHeader);
   hipLaunchKernelGGL(scan_init, dim3((n_segs + 255u) / 256u), dim3(256), 0, s, kind, d_filters, d_segs,
                      n_segs, d_stats, pre);
-  hipLaunchKernelGGL(scan_prefix, dim3(1), dim3(kPrefixThreads), 0, s, pre + 1, n_segs);
+  hipLaunchKernelGGL(prefix_inclusive_u64<kPrefixThreads>, dim3(1), dim3(kPrefixThreads), 0, s, pre + 1, n_segs);
   ScanSlot* slots = reinterpret_cast<ScanSlot*>(static_cast<uint8_t*>(d_workspace) + scan_slots_offset(n_segs));
   const uint32_t grid = kind == TKV_AMQ_BLOOM ? scan_grid<TKV_AMQ_BLOOM>() : scan_grid<TKV_AMQ_VQF>();
   if (kind == TKV_AMQ_BLOOM)

@@ -4,7 +4,8 @@
 //
 //   verify_init     one lane per leaf: the clamped key range, the flags (no filter, the payload's
 //                   src_page_id against the segment's), the result zeroed, the leaf's unit count
-//   verify_prefix   one workgroup: the unit counts' inclusive prefix, in the workspace
+//   prefix_inclusive_u64 (tkv_amq_scan.h)
+//                   one workgroup: the unit counts' inclusive prefix, in the workspace
 //   verify_members_kernel
 //                   one workgroup per unit (up to chunk_keys consecutive keys of one leaf, found
 //                   through the prefix).  The leaf's blocks are copied into LDS with 16-byte
@@ -34,29 +35,9 @@ struct VerifyArgs {
   uint32_t lds_blocks;  // the blocks the launch's dynamic LDS holds
 };
 
-constexpr uint32_t kVerifyPrefixThreads = 1024;
-
 TKV_INLINE bool verify_has_filter(int kind, const tkv_amq_segment& g)
 {
   return g.n_blocks != 0 && (kind == TKV_AMQ_BLOOM ? g.hash_count != 0 : g.tag_bits != 0);
-}
-
-// leaf s's keys [b, e): both ends clamped to n_keys, an end below its begin reads as empty
-TKV_INLINE void verify_leaf_range(const VerifyArgs& a, uint32_t s, const tkv_amq_segment& g, uint64_t& b,
-                                  uint64_t& e)
-{
-  uint64_t lo, hi;
-  if (a.key_begin) {
-    lo = a.key_begin[s];
-    hi = a.key_begin[s + 1];
-  } else {
-    lo = g.key_begin;
-    hi = lo + g.n_keys;
-    if (hi < lo) hi = ~0ull;
-  }
-  b = lo < a.n_keys ? lo : a.n_keys;
-  e = hi < a.n_keys ? hi : a.n_keys;
-  if (e < b) e = b;
 }
 
 __global__ __launch_bounds__(256) void verify_init(int kind, VerifyArgs a)
@@ -71,45 +52,16 @@ __global__ __launch_bounds__(256) void verify_init(int kind, VerifyArgs a)
   uint32_t flags = TKV_AMQ_VERIFY_NO_FILTER;
   uint64_t units = 0;
   if (verify_has_filter(kind, g)) {
-    // the 8 bytes page_id_matches reads: PackedBloomFilterPage @16, PackedVqfFilter @8
-    const uint64_t id =
-        *reinterpret_cast<const uint64_t*>(a.filters + g.out_offset + (kind == TKV_AMQ_BLOOM ? 16 : 8));
+    // the 8 bytes page_id_matches reads
+    const uint64_t id = *reinterpret_cast<const uint64_t*>(a.filters + g.out_offset + src_page_id_offset(kind));
     flags = id != g.src_page_id ? TKV_AMQ_VERIFY_ID_MISMATCH : 0u;
     uint64_t b, e;
-    verify_leaf_range(a, s, g, b, e);
+    segment_key_range(a.key_begin, &g, s, a.n_keys, b, e);
     units = (e - b + a.chunk_keys - 1) / a.chunk_keys;
   }
   // first_missing = ~0 | missing = 0, flags
   *reinterpret_cast<ulonglong2*>(a.result + s) = ulonglong2{~0ull, (uint64_t)flags << 32};
   a.pre[s + 1] = units;
-}
-
-// in-place inclusive scan of v[0 .. n) by one workgroup (the scheme of scan_prefix,
-// tkv_amq_open_scan.hip): a serial run per thread, the runs' sums scanned over the wave with
-// shuffles, the waves' totals through LDS
-__global__ __launch_bounds__(kVerifyPrefixThreads) void verify_prefix(uint64_t* __restrict__ v, uint32_t n)
-{
-  __shared__ uint64_t s_wave[kVerifyPrefixThreads / 64];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint64_t per = ((uint64_t)n + kVerifyPrefixThreads - 1) / kVerifyPrefixThreads;
-  const uint64_t b = per * tid < n ? per * tid : n;
-  const uint64_t e = b + per < n ? b + per : n;
-  uint64_t sum = 0;
-  for (uint64_t i = b; i < e; ++i) sum += v[i];
-  uint64_t inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t up = __shfl_up(inc, o, 64);
-    if ((int)lane >= o) inc += up;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  uint64_t run = inc - sum;
-  for (uint32_t w = 0; w < wave; ++w) run += s_wave[w];
-  for (uint64_t i = b; i < e; ++i) {
-    run += v[i];
-    v[i] = run;
-  }
 }
 
 // Where a leaf's blocks are read from.  words(b): block b as 16 words; bytes(): block 0.
@@ -250,7 +202,7 @@ __global__ __launch_bounds__(NT) void verify_members_kernel(VerifyArgs a)
     const uint32_t s = verify_find_leaf(a.pre, a.n_segs, u, total);
     const tkv_amq_segment g = a.segs[s];
     uint64_t b, e;
-    verify_leaf_range(a, s, g, b, e);
+    segment_key_range(a.key_begin, &g, s, a.n_keys, b, e);
     const uint64_t kb0 = b + (u - a.pre[s]) * a.chunk_keys;
     const uint64_t ke = e - kb0 < a.chunk_keys ? e : kb0 + a.chunk_keys;
     VerifyLeaf lf;
@@ -380,7 +332,7 @@ int tkv_amq_verify_members(int kind, const uint8_t* d_filters, const tkv_amq_seg
   a.lds_blocks = (uint32_t)(lds / 64);
   hipLaunchKernelGGL(verify_init, dim3(n_segs ? (n_segs + 255u) / 256u : 1u), dim3(256), 0, s, kind, a);
   if (n_segs == 0) return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
-  hipLaunchKernelGGL(verify_prefix, dim3(1), dim3(kVerifyPrefixThreads), 0, s, a.pre + 1, n_segs);
+  hipLaunchKernelGGL(prefix_inclusive_u64<kPrefixThreads>, dim3(1), dim3(kPrefixThreads), 0, s, a.pre + 1, n_segs);
   if (n_keys != 0) {
     const uint64_t units = div_up(n_keys, a.chunk_keys) + n_segs;
     const uint32_t grid = (uint32_t)(units < kVerifyMaxGrid ? units : kVerifyMaxGrid);

@@ -8,7 +8,8 @@
 //                      child p.  It counts the entries, keeps the pivot of every depth in the
 //                      workspace (6 bits x 16 depths) and leaves the tile's exclusive prefix in
 //                      path_begin and the tile's total in the workspace.
-//   walk_scan_totals   one workgroup: the tiles' totals to 64-bit exclusive prefixes; the total.
+//   scan_totals<u64>   (tkv_amq_scan.h) one workgroup: the tiles' totals to 64-bit exclusive
+//                      prefixes; the total.
 //   walk_write_kernel  the same descent with the pivots read back: no key is compared again, only
 //                      nodes, bit sets and children are re-read; entries go to their positions.
 //
@@ -23,6 +24,7 @@
 
 #include "tkv_amq.h"
 #include "tkv_amq_device.h"
+#include "tkv_amq_scan.h"
 
 namespace tkv {
 namespace {
@@ -30,18 +32,17 @@ namespace {
 constexpr uint32_t kWalkThreads = 256;
 // the tile loop's workgroups at most: one round of a full machine (256 CUs x 8 workgroups)
 constexpr uint32_t kWalkMaxGrid = 2048;
+// tile totals a thread of the totals scan takes per pass (tests/test_gpu_walk.py sizes the batch
+// that needs a second pass from it)
 constexpr uint32_t kWalkScanPerThread = 4;
-constexpr uint32_t kWalkScanSpan = kWalkThreads * kWalkScanPerThread;  // tile totals per scan pass
 constexpr uint32_t kWalkTrailSplit = 10;  // depths 0..9 in the trail's low word, 10..15 in the high
 
 static_assert(sizeof(tkv_amq_tree_node) == 32 && sizeof(tkv_amq_tree_segment) == 32 &&
                   sizeof(tkv_amq_tree_child) == 16,
               "tree records");
+static_assert(kWalkThreads == kBlockScanThreads && kWalkScanPerThread == kScanTotalsPerThread,
+              "a tile is one block scan; scan_totals' span");
 static_assert(TKV_AMQ_WALK_MAX_DEPTH == 16, "the trail holds 16 pivots of 6 bits");
-
-// kWalk16: both sides fixed 16-byte keys, 16-byte aligned; kWalk24: both fixed 24-byte keys,
-// 8-byte aligned; kWalkAny: everything else (the modes of tkv_amq_find.hip)
-enum WalkMode : int { kWalk16 = 0, kWalk24 = 1, kWalkAny = 2 };
 
 struct WalkArgs {
   const tkv_amq_tree_node* nodes;
@@ -69,96 +70,20 @@ struct WalkArgs {
   uint64_t* tile_total;  // [n_tiles]: totals, then their exclusive prefixes
 };
 
-// The query of one lane, and "pivot key i <= query".
-template <int MODE>
-struct WalkQuery;
-
-template <>
-struct WalkQuery<kWalk16> {
-  uint64_t w0, w1;
-  __device__ inline WalkQuery(const WalkArgs& a, uint64_t i)
-  {
-    const uint4 v = *reinterpret_cast<const uint4*>(a.q + 16 * i);
-    w0 = be64(v.x, v.y);
-    w1 = be64(v.z, v.w);
-  }
-  __device__ inline bool key_le(const WalkArgs& a, uint64_t i) const
-  {
-    const uint4 v = *reinterpret_cast<const uint4*>(a.pk + 16 * i);
-    const uint64_t k0 = be64(v.x, v.y), k1 = be64(v.z, v.w);
-    return k0 < w0 || (k0 == w0 && k1 <= w1);
-  }
-};
-
-template <>
-struct WalkQuery<kWalk24> {
-  uint64_t w0, w1, w2;
-  __device__ inline WalkQuery(const WalkArgs& a, uint64_t i)
-  {
-    const uint64_t* p = reinterpret_cast<const uint64_t*>(a.q + 24 * i);
-    w0 = __builtin_bswap64(p[0]);
-    w1 = __builtin_bswap64(p[1]);
-    w2 = __builtin_bswap64(p[2]);
-  }
-  __device__ inline bool key_le(const WalkArgs& a, uint64_t i) const
-  {
-    const uint64_t* p = reinterpret_cast<const uint64_t*>(a.pk + 24 * i);
-    const uint64_t k0 = __builtin_bswap64(p[0]), k1 = __builtin_bswap64(p[1]), k2 = __builtin_bswap64(p[2]);
-    return k0 < w0 || (k0 == w0 && (k1 < w1 || (k1 == w1 && k2 <= w2)));
-  }
-};
-
-template <>
-struct WalkQuery<kWalkAny> {
-  const uint8_t* p;
-  uint32_t len;
-  __device__ inline WalkQuery(const WalkArgs& a, uint64_t i)
-  {
-    if (a.qoffs) {
-      const uint64_t b = a.qoffs[i];
-      p = a.q + b;
-      len = (uint32_t)(a.qoffs[i + 1] - b);
-    } else {
-      p = a.q + i * a.qstride;
-      len = a.qstride;
-    }
-  }
-  __device__ inline bool key_le(const WalkArgs& a, uint64_t i) const
-  {
-    const uint8_t* k;
-    uint32_t klen;
-    if (a.pkoffs) {
-      const uint64_t b = a.pkoffs[i];
-      k = a.pk + b;
-      klen = (uint32_t)(a.pkoffs[i + 1] - b);
-    } else {
-      k = a.pk + i * a.pkstride;
-      klen = a.pkstride;
-    }
-    return key_compare(k, klen, p, len) <= 0;
-  }
-};
-
 // The pivot of the query in a node that owns keys k0..kp from `key_begin`: the number of interior
 // keys k1..k(p-1) that are <= the query (std::upper_bound over them).  k0 and kp are never read;
 // interior keys at or past n_pk do not exist.
 template <int MODE>
-__device__ inline uint32_t find_pivot(const WalkArgs& a, const WalkQuery<MODE>& q, uint32_t key_begin,
+__device__ inline uint32_t find_pivot(const WalkArgs& a, const OrderedQuery<MODE>& q, uint32_t key_begin,
                                       uint32_t pivot_count)
 {
   const uint64_t first = (uint64_t)key_begin + 1;
   const uint64_t have = first < a.n_pk ? a.n_pk - first : 0;
   uint32_t len = pivot_count - 1;
   len = have < len ? (uint32_t)have : len;
-  // branch-free: lanes in nodes of equal fan-out take the same trip count (at most 6)
-  uint64_t b = first;
-  while (len > 1) {
-    const uint32_t half = len >> 1;
-    b += q.key_le(a, b + half - 1) ? half : 0;
-    len -= half;
-  }
-  if (len == 1) b += q.key_le(a, b) ? 1 : 0;
-  return (uint32_t)(b - first);
+  // lanes in nodes of equal fan-out take the same trip count (at most 6)
+  const KeyArray pk{a.pk, a.pkoffs, a.pkstride};
+  return (uint32_t)(bound(first, len, [&](uint64_t k) { return q.less_equal(pk, k); }) - first);
 }
 
 // The pivots of one walk, 6 bits per depth.
@@ -212,23 +137,25 @@ __device__ inline void walk_tree(const WalkArgs& a, Pivot&& pivot, Entry&& entry
 }
 
 // exclusive scan of v over the workgroup's 256 threads; *total = the sum.  s: 4 words of LDS.
-template <class T>
-__device__ inline T walk_block_scan(T v, T* s, T* total)
+// The scheme of block_exclusive_scan (tkv_amq_scan.h) with the barriers placed differently.  Kept
+// for walk_count_kernel: with the shared scan one of the walk's four timed rows had its median
+// 0.008 ms above the previous code's range (profiles/read_side_shared/README.md).
+__device__ inline uint32_t walk_block_scan(uint32_t v, uint32_t* s, uint32_t* total)
 {
   const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
-  T x = v;
+  uint32_t x = v;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const T y = __shfl_up(x, o, 64);
+    const uint32_t y = __shfl_up(x, o, 64);
     if (lane >= (uint32_t)o) x += y;
   }
   __syncthreads();  // (the previous use of s is over)
   if (lane == 63) s[wave] = x;
   __syncthreads();
-  T base = 0, sum = 0;
+  uint32_t base = 0, sum = 0;
 #pragma unroll
   for (uint32_t w = 0; w < kWalkThreads / 64; ++w) {
-    const T t = s[w];
+    const uint32_t t = s[w];
     if (w < wave) base += t;
     sum += t;
   }
@@ -245,7 +172,7 @@ __global__ __launch_bounds__(kWalkThreads) void walk_count_kernel(WalkArgs a)
     const bool live = i < a.n_queries;
     uint32_t cnt = 0;
     if (live) {
-      const WalkQuery<MODE> q(a, i);
+      const OrderedQuery<MODE> q(KeyArray{a.q, a.qoffs, a.qstride}, i);
       Trail trail;
       walk_tree(
           a,
@@ -258,46 +185,9 @@ __global__ __launch_bounds__(kWalkThreads) void walk_count_kernel(WalkArgs a)
       a.trail[i] = ulonglong2{trail.lo, trail.hi};
     }
     uint32_t total;
-    const uint32_t pre = walk_block_scan<uint32_t>(cnt, s_scan, &total);
+    const uint32_t pre = walk_block_scan(cnt, s_scan, &total);
     if (live) a.path_begin[i] = pre;
     if (threadIdx.x == 0) a.tile_total[t] = total;
-  }
-}
-
-// One workgroup: tile_total[t] <- the sum of the tiles before t, kWalkScanSpan of them per pass
-// with the running base carried over; path_begin[n_queries] <- min(total, capacity); *needed <-
-// the total.  (n_tiles == 0: an empty batch.)
-__global__ __launch_bounds__(kWalkThreads) void walk_scan_totals(uint64_t* __restrict__ tile_total,
-                                                                 uint32_t n_tiles,
-                                                                 uint32_t* __restrict__ path_begin,
-                                                                 uint32_t n_queries, uint32_t capacity,
-                                                                 uint64_t* __restrict__ needed)
-{
-  __shared__ uint64_t s[kWalkThreads / 64];
-  const uint32_t tid = threadIdx.x;
-  uint64_t base = 0;
-  for (uint32_t p0 = 0; p0 < n_tiles; p0 += kWalkScanSpan) {
-    uint64_t v[kWalkScanPerThread];
-    uint64_t sum = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < kWalkScanPerThread; ++r) {
-      const uint64_t t = (uint64_t)p0 + tid * kWalkScanPerThread + r;
-      v[r] = t < n_tiles ? tile_total[t] : 0ull;
-      sum += v[r];
-    }
-    uint64_t total;
-    uint64_t run = base + walk_block_scan<uint64_t>(sum, s, &total);
-#pragma unroll
-    for (uint32_t r = 0; r < kWalkScanPerThread; ++r) {
-      const uint64_t t = (uint64_t)p0 + tid * kWalkScanPerThread + r;
-      if (t < n_tiles) tile_total[t] = run;
-      run += v[r];
-    }
-    base += total;
-  }
-  if (tid == 0) {
-    if (path_begin) path_begin[n_queries] = (uint32_t)min(base, (uint64_t)capacity);
-    if (needed) *needed = base;
   }
 }
 
@@ -400,8 +290,8 @@ int tkv_amq_walk_paths(const tkv_amq_tree_node* nodes, uint64_t n_nodes, const t
   const dim3 block(kWalkThreads);
   if (n_queries == 0) {
     if (d_path_begin || d_needed) {
-      hipLaunchKernelGGL(walk_scan_totals, dim3(1), block, 0, s, static_cast<uint64_t*>(nullptr), 0u,
-                         d_path_begin, 0u, 0u, d_needed);
+      hipLaunchKernelGGL(scan_totals<uint64_t>, dim3(1), block, 0, s, static_cast<uint64_t*>(nullptr), 0u,
+                         d_path_begin, 0u, d_needed);
       return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
     }
     return TKV_AMQ_OK;
@@ -434,18 +324,14 @@ int tkv_amq_walk_paths(const tkv_amq_tree_node* nodes, uint64_t n_nodes, const t
   a.needed = d_needed;
   a.trail = reinterpret_cast<ulonglong2*>(ws + l.trail_off);
   a.tile_total = reinterpret_cast<uint64_t*>(ws + l.totals_off);
-  // the fast modes, chosen as tkv_amq_find_keys chooses them
-  const bool fixed = !query_offsets && !pivot_key_offsets && query_stride == pivot_key_stride;
-  const uintptr_t both = reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(pivot_keys);
-  const int mode = fixed && query_stride == 16 && !(both & 15) ? kWalk16
-                   : fixed && query_stride == 24 && !(both & 7) ? kWalk24
-                                                                : kWalkAny;
+  const int mode = key_order_mode(KeyArray{queries, query_offsets, query_stride},
+                                  KeyArray{pivot_keys, pivot_key_offsets, pivot_key_stride});
   const dim3 grid(a.n_tiles < kWalkMaxGrid ? a.n_tiles : kWalkMaxGrid);
-  if (mode == kWalk16) hipLaunchKernelGGL(walk_count_kernel<kWalk16>, grid, block, 0, s, a);
-  else if (mode == kWalk24) hipLaunchKernelGGL(walk_count_kernel<kWalk24>, grid, block, 0, s, a);
-  else hipLaunchKernelGGL(walk_count_kernel<kWalkAny>, grid, block, 0, s, a);
-  hipLaunchKernelGGL(walk_scan_totals, dim3(1), block, 0, s, a.tile_total, a.n_tiles, d_path_begin,
-                     a.n_queries, a.capacity, d_needed);
+  if (mode == kOrder16) hipLaunchKernelGGL(walk_count_kernel<kOrder16>, grid, block, 0, s, a);
+  else if (mode == kOrder24) hipLaunchKernelGGL(walk_count_kernel<kOrder24>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(walk_count_kernel<kOrderAny>, grid, block, 0, s, a);
+  hipLaunchKernelGGL(scan_totals<uint64_t>, dim3(1), block, 0, s, a.tile_total, a.n_tiles,
+                     d_path_begin + a.n_queries, a.capacity, d_needed);
   hipLaunchKernelGGL(walk_write_kernel, grid, block, 0, s, a);
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
