@@ -98,13 +98,18 @@ __device__ inline uint64_t drotl(uint64_t x)
   return mk64(__builtin_amdgcn_alignbit(l, h, 32 - R), __builtin_amdgcn_alignbit(h, l, 32 - R));
 }
 
+// S >= 32: one 32-bit shift of the high word.  S < 32: the plain 64-bit shift, one v_lshrrev_b64
+// whose two words feed the two xors of `h ^= h >> S`.  (Spelled in halves, alignbit for the low
+// word and `hi >> S` for the high, LLVM widens the high half back into a v_lshrrev_b64 and keeps
+// the v_alignbit_b32 beside it: one VALU more per avalanche.)
 template <int S>
 __device__ inline uint64_t dshr(uint64_t x)
 {
+  static_assert(S > 0 && S < 64, "shift amount");
   if constexpr (S >= 32) {
     return (uint64_t)(hi32(x) >> (S - 32));
   } else {
-    return mk64(__builtin_amdgcn_alignbit(hi32(x), lo32(x), S), hi32(x) >> S);
+    return x >> S;
   }
 }
 

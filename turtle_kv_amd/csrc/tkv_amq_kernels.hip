@@ -399,8 +399,9 @@ __device__ inline void write_page_header(uint8_t* out, const tkv_amq_segment& sg
 // sees the 32-bit offset's zero-extension only there; hoisted, it costs a v_lshl_add_u64 per load.
 // These asms, the ones in bloom_insert (the opaque block, the two v_bfi_b32 of the strided image)
 // and the leaf loops' sched_barrier hold an instruction form no test sees: after a compiler update
-// rerun the check in profiles/lds_stride/README.md ("After a ROCm update"; tools/isa_loops.py:
-// 952 / 1,072 and 608 / 684 v_* per full-chunk loop; 972 / 1,096 and 618 / 696 before the strided
+// rerun the check in profiles/avalanche_shift/README.md ("After a ROCm update"; tools/isa_loops.py:
+// 920 / 1,036 and 592 / 666 v_* per full-chunk loop; 948 / 1,068 and 606 / 682 while dshr<29> was
+// spelled in halves, profiles/lds_stride/README.md; 972 / 1,096 and 618 / 696 before the strided
 // image, profiles/leaf_loop/README.md).
 TKV_INLINE uint64_t sgpr_addr(const uint8_t* base)
 {
