@@ -53,6 +53,12 @@
  *                           tree/algo/segmented_levels.hpp:340-369): each lookup's ordered list of
  *                           leaves, with page ids, flushed item upper bounds (packed_node_page.cpp:
  *                           231-248) and (depth, level) per entry
+ *   tkv_amq_get_keys        the three above in one call and in the reference's order: the whole
+ *                           point lookup (NodeAlgorithms::find_key, tree/algo/nodes.hpp:158-187) with
+ *                           both of its stopping rules -- the first level that yields the key ends
+ *                           it, and an item found below a segment's flushed item upper bound
+ *                           (SegmentAlgorithms::find_key, tree/algo/segments.hpp:166-206) leaves the
+ *                           level -- and KeyQuery::Metrics over the filters the reference asks
  *   tkv_amq_open_filters    what KeyQuery::reject_page reads from a loaded filter page instead
  *                           of a plan (tree/key_query.hpp:149-247): check_magic()
  *                           (vqf_filter_page_view.hpp:96-100), src_page_id, block_count,
@@ -672,7 +678,8 @@ int tkv_amq_find_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment*
  * is the unclamped total, so a caller sees a short capacity and can retry.  The output is a
  * function of the input: no atomics.  d_path_flushed and d_path_where are for a search that knows
  * the reference's rule "found below the flushed bound: skip the rest of the level"
- * (tree/algo/segments.hpp:185-200); tkv_amq_find_keys does not read them yet.
+ * (tree/algo/segments.hpp:185-200); tkv_amq_find_keys does not read them: tkv_amq_get_keys is the
+ * call that applies the rule (it takes the bounds from the tree itself).
  * Malformed trees get a defined answer and never an out-of-range read:
  *  - interior keys at or past n_pivot_keys do not exist (the search runs over those that do)
  *  - a level's segment range is clamped to n_segments; level_start[l+1] < level_start[l] reads as
@@ -737,6 +744,99 @@ int tkv_amq_walk_paths(const tkv_amq_tree_node* nodes, uint64_t n_nodes,
                        uint64_t* d_path_page_id, uint32_t* d_path_flushed, uint16_t* d_path_where,
                        uint64_t path_capacity, uint64_t* d_needed, void* d_workspace,
                        uint64_t workspace_bytes, void* stream);
+
+/* Fused point lookup: a batch of lookups from the root to the found key in one call
+ * (NodeAlgorithms::find_key, tree/algo/nodes.hpp:158-187: levels newest first, then the child,
+ * ended at the first level that yields the key; SegmentedLevelAlgorithms::find_key, tree/algo/
+ * segmented_levels.hpp:340-369; SegmentAlgorithms::find_key, tree/algo/segments.hpp:166-206: an
+ * item found below the segment's flushed item upper bound for the pivot "has been flushed from
+ * this segment", kBreak; reject_page, tree/key_query.hpp:149-247; find_key_in_leaf_impl,
+ * tree/key_query.cpp:27-80,299-327).  It computes what tkv_amq_walk_paths ->
+ * tkv_amq_path_probe -> tkv_amq_find_keys compute for a tree without flushed bounds, and the
+ * reference's answer for one with them; it writes no path, asks no filter below a hit and
+ * counts KeyQuery::Metrics over the filters the reference would have asked.
+ * Arguments: kind / d_filters / d_segs / n_segs as the probes take them; the flat tree, the pivot
+ * keys and the queries exactly as tkv_amq_walk_paths takes them; leaf_keys .. d_key_begin exactly
+ * as tkv_amq_find_keys takes them (the precondition on the leaves' order included).
+ * Per query, from node 0 at depth 0:
+ *  1. p = the pivot, as tkv_amq_walk_paths step 1 defines it.  Every clamp and stop for malformed
+ *     trees listed there applies unchanged: the lookup ends with what it has so far.
+ *  2. for level 0 .. level_count-1, for each segment of the level in order whose active_pivots bit
+ *     p is set: VISIT (seg.leaf, seg.leaf_page_id) with bound = the segment's flushed bound for p
+ *     (tkv_amq_walk_paths' definition: bit_rank, an index at or past n_flushed_bounds reads 0)
+ *  3. child p: under height <= 1 VISIT (index, page_id) with bound 0 and end; otherwise go on in
+ *     node `index` at depth + 1.
+ * A VISIT of (leaf, page id) with a bound:
+ *  - the filter is asked exactly as tkv_amq_path_probe asks an entry: the key is hashed once per
+ *    query, before its first test; answer 0 = the filter rejects, 1 = maybe or cannot reject
+ *    (leaf >= n_segs, a segment without a filter, a page id mismatch, a VQF hash dropped by
+ *    hash_val_shift), from the same code.  With TKV_AMQ_GET_CHECK_PAGE_ID the id compared with the
+ *    filter's stored one is the tree's own (leaf_page_id / page_id); without it no id is read and
+ *    d_filters is read only for filter bytes.  One count per visit goes into d_metrics,
+ *    classified as tkv_amq_probe_ex classifies a pair.
+ *  - answer 0: the next entry.
+ *  - answer 1, leaf >= n_segs: UNSEARCHABLE; the next entry.
+ *  - answer 1 otherwise: the lower bound of the query in the leaf's range (range, clamp and order
+ *    are tkv_amq_find_keys'; the first of equal keys).  Key not there: ABSENT, and if the visit's
+ *    class was "checked", filter_false_positive_count + 1; the next entry.  Key there at global
+ *    index b, index_in_leaf = b - the leaf's clamped range begin:
+ *      index_in_leaf < bound   FLUSHED: the level is left -- its remaining segments are not
+ *                              visited, asked or counted -- and the lookup goes on with the next
+ *                              level or the child
+ *      otherwise               FOUND: the result is written and the lookup ends
+ *  d_result[n_queries]        (device, 16-byte aligned) written for every query
+ *  d_query_visits[n_queries]  (device, or NULL) the number of visits of each query
+ *  d_metrics, d_counts        (device, 8-byte aligned, or NULL) ADDED to with atomics, one per
+ *                             non-zero counter per wave; zero them to reset
+ * A wave sums its lanes' tallies in 32 bits before its one add per counter at the end of the launch:
+ * the counters are exact while no wave visits 2^32 entries in one call (a wave takes 64 queries of
+ * every 524,288; 25M lookups of 24.5 visits: 75 thousand per wave).
+ * Integer atomics on the counters only: the output is a function of the input.  n_nodes == 0:
+ * every result is "none" and every visit count 0.  One lane per query; 16-byte keys (all three key
+ * sides fixed, 16-byte aligned) and 24-byte keys (all fixed, 8-byte aligned) are compared as
+ * big-endian words, any other combination from memory; the hash takes the query side's shape as
+ * tkv_amq_path_probe does.
+ * Asynchronous on `stream`: one kernel launch, no workspace, no allocation, no synchronisation;
+ * capturable.  n_queries == 0 is OK.
+ * InvalidArgument, judged before a device is looked for: unknown kind; unknown flag bits; n_nodes,
+ * n_segments, n_children, n_flushed_bounds, n_pivot_keys or n_queries above 0xffffffff; a null
+ * nodes / segments / children / d_flushed_bounds / pivot_keys / leaf_keys with its count non-zero;
+ * a null d_segs or d_filters with n_segs > 0; a null queries or d_result with n_queries > 0; a
+ * fixed key form (no offsets) with stride 0, on any of the three key sides; nodes, segments,
+ * children or d_result not 16-byte aligned; d_metrics or d_counts not 8-byte aligned;
+ * d_query_visits not 4-byte aligned; fixed 16-byte queries that are not 16-byte aligned
+ * (tkv_amq_path_probe's rule).  A valid call on a machine without a device returns Unavailable. */
+typedef struct tkv_amq_get_result { /* 16 bytes */
+  uint64_t key_index; /* global index (into leaf_keys) of the found key; ~0ull if not found */
+  uint32_t leaf;      /* the segment that holds it; 0xffffffff if none */
+  uint32_t where;     /* depth << 8 | level of the entry that held it (level 0xff: the child leaf,
+                         as d_path_where); 0xffffffff if none */
+} tkv_amq_get_result;
+
+typedef struct tkv_amq_get_counts { /* 48 bytes, u64 each, ADDED to with atomics (zero to reset) */
+  uint64_t visit_count;        /* entries visited (== total_filter_query_count) */
+  uint64_t leaf_search_count;  /* visits that searched their leaf */
+  uint64_t found_count;        /* queries that found their key */
+  uint64_t absent_count;       /* searches that did not find the key */
+  uint64_t unsearchable_count; /* visits that answered 1 and name no leaf of the plan */
+  uint64_t flushed_count;      /* searches that found the key below the flushed bound */
+} tkv_amq_get_counts;
+
+#define TKV_AMQ_GET_CHECK_PAGE_ID 0x1u /* compare each filter's stored page id with the tree's */
+
+int tkv_amq_get_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs, uint32_t n_segs,
+                     const tkv_amq_tree_node* nodes, uint64_t n_nodes,
+                     const tkv_amq_tree_segment* segments, uint64_t n_segments,
+                     const tkv_amq_tree_child* children, uint64_t n_children,
+                     const uint32_t* d_flushed_bounds, uint64_t n_flushed_bounds,
+                     const uint8_t* pivot_keys, const uint64_t* pivot_key_offsets,
+                     uint32_t pivot_key_stride, uint64_t n_pivot_keys,
+                     const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
+                     uint64_t n_queries,
+                     const uint8_t* leaf_keys, const uint64_t* leaf_key_offsets, uint32_t leaf_key_stride,
+                     uint64_t n_leaf_keys, const uint64_t* d_key_begin,
+                     uint32_t flags, tkv_amq_get_result* d_result, uint32_t* d_query_visits,
+                     tkv_amq_probe_metrics* d_metrics, tkv_amq_get_counts* d_counts, void* stream);
 
 /* Open built filters without a plan (a store restarting on a checkpoint, filter pages received
  * from elsewhere): reconstructs and validates one segment per filter from the filter bytes on

@@ -20,6 +20,8 @@
 //                                                                          open_filter_pages, scan_filters
 //   find_pivot_containing / find_key      tree/algo/nodes.hpp:48-71,158-187, tree/algo/segmented_levels.hpp:340-369
 //                                                                          TreeIndex, KeyQuery::walk_paths
+//   NodeAlgorithms::find_key, whole       tree/algo/nodes.hpp:158-187, tree/algo/segments.hpp:166-206
+//                                                                          TreeIndex::get_host, KeyQuery::get_keys
 //
 // The single-leaf functions take the leaf's keys as host string views (the reference's
 // `items` range of EditView keys, tombstones included) and fill a host page payload
@@ -1282,6 +1284,52 @@ class TreeIndex
     }
   }
 
+  // The whole point lookup on the host (what tkv_amq_get_keys computes, include/tkv_amq.h): the
+  // entries of walk_host in order; maybe(leaf, key) stands for the leaf's filter (false: the filter
+  // rejects) and defaults to "always maybe", which gives the same results as any filter without
+  // false negatives; a leaf that may hold the key is searched with std::lower_bound over
+  // leaf_keys [key_begin[leaf], key_begin[leaf + 1]) (a leaf at or past key_begin.size() - 1
+  // cannot be searched); a key found below the entry's flushed bound leaves the level; the first
+  // key found at or above it ends the lookup.  visits (optional): the entries each key visited.
+  template <class Maybe>
+  void get_host(const std::vector<std::string_view>& keys, const std::vector<std::string_view>& leaf_keys,
+                const std::vector<u64>& key_begin, std::vector<tkv_amq_get_result>& out, Maybe&& maybe,
+                std::vector<u32>* visits = nullptr) const
+  {
+    out.assign(keys.size(), tkv_amq_get_result{~u64{0}, ~u32{0}, ~u32{0}});
+    if (visits) visits->assign(keys.size(), 0);
+    std::vector<std::string_view> pk(pivot_keys_.begin(), pivot_keys_.end());
+    const usize n_leaves = key_begin.empty() ? 0 : key_begin.size() - 1;
+    TreePaths o;
+    for (usize i = 0; i < keys.size(); ++i) {
+      o.clear(0);
+      walk_one(pk, keys[i], o);
+      u32 left = ~u32{0}, n_visits = 0;  // the level that was left (a `where`), if any
+      for (usize e = 0; e < o.leaf.size(); ++e) {
+        if (o.where[e] == left) continue;
+        ++n_visits;
+        const u32 leaf = o.leaf[e];
+        if (!maybe(leaf, keys[i]) || leaf >= n_leaves) continue;
+        const u64 b0 = std::min<u64>(key_begin[leaf], leaf_keys.size());
+        const u64 e0 = std::max<u64>(std::min<u64>(key_begin[leaf + 1], leaf_keys.size()), b0);
+        const u64 b = (u64)(std::lower_bound(leaf_keys.begin() + b0, leaf_keys.begin() + e0, keys[i]) - leaf_keys.begin());
+        if (b == e0 || leaf_keys[b] != keys[i]) continue;
+        if (b - b0 < o.flushed[e]) {
+          left = o.where[e];
+          continue;
+        }
+        out[i] = tkv_amq_get_result{b, leaf, o.where[e]};
+        break;
+      }
+      if (visits) (*visits)[i] = n_visits;
+    }
+  }
+  void get_host(const std::vector<std::string_view>& keys, const std::vector<std::string_view>& leaf_keys,
+                const std::vector<u64>& key_begin, std::vector<tkv_amq_get_result>& out) const
+  {
+    get_host(keys, leaf_keys, key_begin, out, [](u32, std::string_view) { return true; });
+  }
+
   // The flat arrays on the device, uploaded once (pivot keys fixed-stride if they share a length).
   Status upload()
   {
@@ -1314,6 +1362,22 @@ class TreeIndex
                               keys_fixed_ ? key_stride_ : 0, pivot_keys_.size(), d_queries, d_query_offsets,
                               query_stride, n_queries, d_path_begin, d_path_leaf, d_path_page_id, d_path_flushed,
                               d_path_where, path_capacity, d_needed, d_workspace, workspace_bytes, stream);
+  }
+
+  // tkv_amq_get_keys over the uploaded tree (upload() first); every pointer is a device pointer
+  int get_device(int kind, const u8* d_filters, const tkv_amq_segment* d_segs, u32 n_segs, const u8* d_queries,
+                 const u64* d_query_offsets, u32 query_stride, u64 n_queries, const u8* d_leaf_keys,
+                 const u64* d_leaf_key_offsets, u32 leaf_key_stride, u64 n_leaf_keys, const u64* d_key_begin,
+                 u32 flags, tkv_amq_get_result* d_result, u32* d_query_visits, tkv_amq_probe_metrics* d_metrics,
+                 tkv_amq_get_counts* d_counts, hipStream_t stream = nullptr) const
+  {
+    return tkv_amq_get_keys(kind, d_filters, d_segs, n_segs, d_nodes_.get<tkv_amq_tree_node>(), nodes_.size(),
+                            d_segments_.get<tkv_amq_tree_segment>(), segments_.size(),
+                            d_children_.get<tkv_amq_tree_child>(), children_.size(), d_bounds_.get<u32>(),
+                            flushed_bounds_.size(), d_keys_.get(), keys_fixed_ ? nullptr : d_key_offs_.get<u64>(),
+                            keys_fixed_ ? key_stride_ : 0, pivot_keys_.size(), d_queries, d_query_offsets,
+                            query_stride, n_queries, d_leaf_keys, d_leaf_key_offsets, leaf_key_stride, n_leaf_keys,
+                            d_key_begin, flags, d_result, d_query_visits, d_metrics, d_counts, stream);
   }
 
  private:
@@ -1698,6 +1762,64 @@ class KeyQuery
         hipMemcpy(&pm, d_metrics.get(), sizeof(pm), hipMemcpyDeviceToHost) != hipSuccess)
       return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy found keys");
     metrics().filter_false_positive_count.add(pm.filter_false_positive_count);
+    return OkStatus();
+  }
+
+  // The whole lookup in one call (tkv_amq_get_keys): walk_paths, candidate_leaves and
+  // find_in_leaves fused, in the reference's order and with its flushed-bound rule -- what
+  // TreeIndex::get_host computes on the host.  No path is materialised, and nothing below a hit
+  // is visited or counted.
+  //  d_filters, d_segs, segs   as for candidate_leaves
+  //  d_leaf_keys, ...          as for find_in_leaves
+  //  check_page_ids            compare each filter's stored page id with the tree's id of the leaf
+  //  out                       (out) per key: the found key's global index, its leaf and
+  //                            depth << 8 | level of the entry that held it; ~0 / 0xffffffff if none
+  //  counts                    (out, optional) the lookup's own tallies
+  // Adds every visit to metrics(), classified as reject_page classifies it, the false positives
+  // included: no host truth is needed.
+  Status get_keys(FilterKind kind, const u8* d_filters, const tkv_amq_segment* d_segs,
+                  const std::vector<tkv_amq_segment>& segs, TreeIndex& tree, const u8* d_leaf_keys,
+                  const u64* d_leaf_key_offsets, u32 leaf_key_stride, u64 n_leaf_keys, bool check_page_ids,
+                  std::vector<tkv_amq_get_result>& out, tkv_amq_get_counts* counts = nullptr)
+  {
+    const u64 n = keys_.size();
+    out.assign(n, tkv_amq_get_result{~u64{0}, ~u32{0}, ~u32{0}});
+    if (counts) *counts = tkv_amq_get_counts{};
+    if (tkv_amq_device_count() == 0) return Status::from(TKV_AMQ_UNAVAILABLE, "no HIP device");
+    if (n == 0) return OkStatus();
+    TKV_AMQ_REQUIRE_OK(tree.upload());
+    DeviceBuffer d_keys, d_offs, d_result, d_tallies;
+    constexpr usize kMetricsBytes = sizeof(tkv_amq_probe_metrics);
+    if (!d_result.resize(sizeof(tkv_amq_get_result) * n) || !d_tallies.resize(kMetricsBytes + sizeof(tkv_amq_get_counts)))
+      return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+    bool fixed = false;
+    u32 stride = 16;
+    TKV_AMQ_REQUIRE_OK(detail::stage_keys(keys_, d_keys, d_offs, fixed, stride));
+    if (hipMemset(d_tallies.get(), 0, kMetricsBytes + sizeof(tkv_amq_get_counts)) != hipSuccess)
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemset counters");
+    auto* d_metrics = d_tallies.get<tkv_amq_probe_metrics>();
+    auto* d_counts = reinterpret_cast<tkv_amq_get_counts*>(d_tallies.get() + kMetricsBytes);
+    const int st = tree.get_device((int)kind, d_filters, d_segs, (u32)segs.size(), d_keys.get(),
+                                   fixed ? nullptr : d_offs.get<u64>(), fixed ? stride : 0, n, d_leaf_keys,
+                                   d_leaf_key_offsets, leaf_key_stride, n_leaf_keys, nullptr,
+                                   check_page_ids ? TKV_AMQ_GET_CHECK_PAGE_ID : 0u,
+                                   d_result.get<tkv_amq_get_result>(), nullptr, d_metrics, d_counts);
+    if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_get_keys");
+    tkv_amq_probe_metrics pm{};
+    tkv_amq_get_counts gc{};
+    // (blocking copies on the null stream: they wait for the lookup)
+    if (hipMemcpy(out.data(), d_result.get(), sizeof(tkv_amq_get_result) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&pm, d_metrics, sizeof(pm), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&gc, d_counts, sizeof(gc), hipMemcpyDeviceToHost) != hipSuccess)
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy found keys");
+    if (counts) *counts = gc;
+    Metrics& m = metrics();
+    m.total_filter_query_count.add(pm.total_filter_query_count);
+    m.no_filter_page_count.add(pm.no_filter_page_count);
+    m.page_id_mismatch_count.add(pm.page_id_mismatch_count);
+    m.filter_reject_count.add(pm.filter_reject_count);
+    m.filter_positive_count.add(pm.filter_positive_count);
+    m.filter_false_positive_count.add(pm.filter_false_positive_count);
     return OkStatus();
   }
 

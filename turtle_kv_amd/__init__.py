@@ -17,7 +17,8 @@ from .filters import (BoolStatus, FilterPage, FilterPlan, KeyBatch, KeyQuery, Pa
                       scan_filters_workspace_bytes, filter_fill, verify_members,
                       verify_members_device, verify_members_workspace_bytes, find_keys,
                       find_keys_device, FindResult, FindCounts, TreeIndex, WalkResult, walk_paths,
-                      walk_paths_device, walk_paths_workspace_bytes)
+                      walk_paths_device, walk_paths_workspace_bytes, get_keys, get_keys_device,
+                      GetResult, GetCounts)
 
 __all__ = [
     "abi", "BLOOM", "VQF", "TkvAmqError", "BoolStatus", "FilterPage", "FilterPlan", "KeyBatch",
@@ -33,4 +34,5 @@ __all__ = [
     "scan_filters_workspace_bytes", "filter_fill", "verify_members", "verify_members_device",
     "verify_members_workspace_bytes", "find_keys", "find_keys_device", "FindResult", "FindCounts",
     "TreeIndex", "WalkResult", "walk_paths", "walk_paths_device", "walk_paths_workspace_bytes",
+    "get_keys", "get_keys_device", "GetResult", "GetCounts",
 ]

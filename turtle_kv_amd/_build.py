@@ -23,6 +23,7 @@ SOURCES = [os.path.join(HERE, "csrc", "tkv_amq_kernels.hip"),
 DEPS = SOURCES + [os.path.join(HERE, "csrc", "tkv_amq_device.h"),
                   os.path.join(HERE, "csrc", "tkv_amq_key_order.h"),  # (included by tkv_amq_device.h)
                   os.path.join(HERE, "csrc", "tkv_amq_scan.h"),  # (kernels, open_scan and walk units)
+                  os.path.join(HERE, "csrc", "tkv_amq_tree_walk.h"),  # (kernels and walk units)
                   os.path.join(HERE, "csrc", "tkv_amq_lds_stride.h"),  # (included by tkv_amq_kernels.hip)
                   os.path.join(HERE, "csrc", "tkv_amq_verify.h"),  # (included by tkv_amq_kernels.hip)
                   os.path.join(ROOT, "include", "tkv_amq.h")]

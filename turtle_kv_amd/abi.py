@@ -99,6 +99,7 @@ EXPORTS = [
     "tkv_amq_verify_members_ws_bytes", "tkv_amq_verify_members",
     "tkv_amq_find_keys",
     "tkv_amq_walk_paths_ws_bytes", "tkv_amq_walk_paths",
+    "tkv_amq_get_keys",
 ]
 
 # tkv_amq_build_route: TKV_AMQ_ROUTE_* (a Bloom batch's route, or a VQF batch's decide stage),
@@ -150,6 +151,15 @@ CAND_ABSENT, CAND_FOUND, CAND_NOT_SEARCHED, CAND_UNSEARCHABLE = range(4)
 NOT_FOUND = (1 << 64) - 1  # key_index of a query whose key no searched candidate holds
 NO_LEAF = 0xFFFFFFFF       # its leaf and cand
 
+# tkv_amq_get_result (16 bytes), tkv_amq_get_counts (48 bytes) and TKV_AMQ_GET_CHECK_PAGE_ID
+GET_RESULT_DTYPE = np.dtype([("key_index", "<u8"), ("leaf", "<u4"), ("where", "<u4")])
+assert GET_RESULT_DTYPE.itemsize == 16
+GET_COUNTS_FIELDS = ("visit_count", "leaf_search_count", "found_count", "absent_count",
+                     "unsearchable_count", "flushed_count")
+GET_COUNTS_DTYPE = np.dtype([(n, "<u8") for n in GET_COUNTS_FIELDS])
+assert GET_COUNTS_DTYPE.itemsize == 48
+GET_CHECK_PAGE_ID = 0x1
+NO_WHERE = 0xFFFFFFFF      # `where` of a query that found nothing
 
 
 # tkv_amq_walk_paths: the flat tree (tkv_amq_tree_node / _segment / _child) and its limits
@@ -321,6 +331,13 @@ def lib(build_if_missing: bool = True):
         L.tkv_amq_walk_paths.restype = i32
         L.tkv_amq_walk_paths.argtypes = [vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, u32, u64, vp, vp, u32,
                                          u64, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp]
+    if hasattr(L, "tkv_amq_get_keys"):
+        L.tkv_amq_get_keys.restype = i32
+        L.tkv_amq_get_keys.argtypes = [i32, vp, vp, u32,
+                                       vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, u32, u64,
+                                       vp, vp, u32, u64,
+                                       vp, vp, u32, u64, vp,
+                                       u32, vp, vp, vp, vp, vp]
     if hasattr(L, "tkv_amq_bloom_route"):
         L.tkv_amq_bloom_route_ws_bytes.restype = u64
         L.tkv_amq_bloom_route_ws_bytes.argtypes = [u64, u32]

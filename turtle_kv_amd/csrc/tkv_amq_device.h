@@ -442,4 +442,16 @@ __device__ inline bool page_id_matches(const uint8_t* payload, uint32_t id_off, 
   return ids == nullptr || *reinterpret_cast<const uint64_t*>(payload + id_off) == ids[i];
 }
 
+// the same for a caller that holds the page id itself (tkv_amq_get_keys: the tree's own id of the
+// leaf); check == false reads nothing and matches
+struct PageIdIs {
+  uint64_t id;
+  bool check;
+};
+
+__device__ inline bool page_id_matches(const uint8_t* payload, uint32_t id_off, const PageIdIs& want, uint64_t)
+{
+  return !want.check || *reinterpret_cast<const uint64_t*>(payload + id_off) == want.id;
+}
+
 }  // namespace tkv

@@ -44,6 +44,7 @@
 #include "tkv_amq_device.h"
 #include "tkv_amq_lds_stride.h"
 #include "tkv_amq_scan.h"
+#include "tkv_amq_tree_walk.h"
 
 // The one diagnostic build option (TKV_DIAG_RING: per-step timestamps of vqf_ring_place's
 // decider, read by tools/ring_diag.py) is for experiment libraries only; the shipped library
@@ -4708,12 +4709,13 @@ __device__ inline bool vqf_present(const uint8_t* payload, uint32_t n_blocks, ui
   return vqf_present_at<T>(payload + kVqfHeader + kVqfMetadata, n_blocks, magic, h);
 }
 
-// One VQF (hash, leaf) test: result bit | class << 1.
+// One VQF (hash, leaf) test: result bit | class << 1.  Ids: where the page id to compare comes
+// from, the probes' array indexed by i or the fused lookup's PageIdIs (page_id_matches).
 // (always inlined: out of line it was a real call in every probe kernel, with a stack frame)
-template <bool kOpts>
+template <bool kOpts, typename Ids = const uint64_t*>
 __device__ __attribute__((always_inline)) inline uint32_t vqf_probe_one(const uint8_t* filters, const tkv_amq_segment* segs,
                                          uint32_t n_segs, uint32_t s, uint64_t h,
-                                         const uint64_t* page_ids = nullptr, uint64_t i = 0)
+                                         Ids page_ids = nullptr, uint64_t i = 0)
 {
   const ProbeDesc d = load_probe_desc(segs, s, n_segs);
   if (d.tag_bits == 0) return 1u | (kNoFilter << 1);  // no filter: cannot reject
@@ -4970,11 +4972,11 @@ struct BloomEntry16 {
   __device__ inline uint32_t cls() const { return k_cls >> 16; }
 };
 
-template <bool kOpts>
+template <bool kOpts, typename Ids>
 __device__ inline BloomEntry16 bloom_entry16_fetch(const uint8_t* __restrict__ filters,
                                                    const tkv_amq_segment* __restrict__ segs,
                                                    uint32_t n_segs, uint32_t leaf, uint64_t h0,
-                                                   const uint64_t* page_ids, uint32_t ent)
+                                                   Ids page_ids, uint32_t ent)
 {
   BloomEntry16 f;
   const ProbeDesc d = load_probe_desc(segs, leaf, n_segs);
@@ -5061,12 +5063,32 @@ __device__ inline uint32_t bloom_entry16_test(uint64_t h0, const BloomBits16& bi
   return (ok & 1u) | (f.cls() << 1);
 }
 
-// Keys of other shapes: bloom_probe_item's test with the bit index of hash j supplied by the
-// caller (finished again from the shared lane rounds, or read from the lane's cache).
-template <bool kOpts, typename BitFn>
+// Keys of other shapes: the bit index of hash j of one query, for every filter on its way.
+// Under 32 bytes the seed-independent lane rounds are shared by every hash of every filter.  A
+// longer key's every hash reads the whole key: bit index j is computed when the first filter with
+// more than j hashes comes by, and kept in the lane's LDS slot (`cache`).
+template <typename H>
+struct BloomBitSource {
+  const H& x;
+  uint16_t* cache;
+  uint32_t have = 1;
+  __device__ inline uint32_t operator()(uint32_t j, [[maybe_unused]] uint32_t k)
+  {
+    if constexpr (kBloomShared<H>) {
+      return x.bit(j) & kBloomBitMask;
+    } else {
+      for (const uint32_t want = min(k, kMaxBloomHashes); have < want; ++have)
+        cache[have] = (uint16_t)(x.bit(have) & kBloomBitMask);
+      return (uint32_t)cache[min(j, kMaxBloomHashes - 1)];
+    }
+  }
+};
+
+// bloom_probe_item's test with the bit index of hash j supplied by the caller (a BloomBitSource).
+template <bool kOpts, typename Ids, typename BitFn>
 __device__ inline uint32_t bloom_entry_test(const uint8_t* __restrict__ filters,
                                             const tkv_amq_segment* __restrict__ segs, uint32_t n_segs,
-                                            uint32_t leaf, uint64_t h0, const uint64_t* page_ids,
+                                            uint32_t leaf, uint64_t h0, Ids page_ids,
                                             uint32_t ent, BitFn&& bit_of)
 {
   const ProbeDesc d = load_probe_desc(segs, leaf, n_segs);
@@ -5143,20 +5165,7 @@ __global__ __launch_bounds__(256, (MODE == kKey16 && !kOpts ? 8 : 4)) void path_
       } else {
         with_bloom_key_at<MODE>(a.q, a.qoffs, a.stride, i, [&](const auto& x) {
           const uint64_t h0 = x.h0();
-          // Under 32 bytes the seed-independent lane rounds are shared by every hash of every
-          // filter.  A longer key's every hash reads the whole key: bit index j is computed when
-          // the first filter with more than j hashes comes by, and kept in the lane's LDS slot.
-          [[maybe_unused]] uint16_t* cache = reinterpret_cast<uint16_t*>(slot);
-          [[maybe_unused]] uint32_t have = 1;
-          auto bit_of = [&](uint32_t j, [[maybe_unused]] uint32_t k) {
-            if constexpr (kBloomShared<std::decay_t<decltype(x)>>) {
-              return x.bit(j) & kBloomBitMask;
-            } else {
-              for (const uint32_t want = min(k, kMaxBloomHashes); have < want; ++have)
-                cache[have] = (uint16_t)(x.bit(have) & kBloomBitMask);
-              return (uint32_t)cache[min(j, kMaxBloomHashes - 1)];
-            }
-          };
+          BloomBitSource<std::decay_t<decltype(x)>> bit_of{x, reinterpret_cast<uint16_t*>(slot)};
           for (uint32_t ent = b; ent < e; ++ent) {
             const uint32_t leaf1 = ent + 1 < e ? a.path_leaf[ent + 1] : 0u;
             const uint32_t r = bloom_entry_test<kOpts>(a.filters, a.segs, a.n_segs, leaf, h0,
@@ -5208,6 +5217,196 @@ __global__ __launch_bounds__(256) void path_scatter(PathArgs a)
       ++pos;
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// Fused point lookup (tkv_amq_get_keys): descent, filter tests and leaf searches in one lane
+// ---------------------------------------------------------------------------------------
+// One lane per query (workgroup tiles of 256, a bounded grid striding over them).  The lane runs
+// the reference's find_key (tree/algo/nodes.hpp:158-187) as the reference orders it: walk_tree
+// names the entries; each entry is one filter test with the path probe's helpers and, if the
+// filter says maybe, one lower bound over the leaf's keys (find_keys_kernel's); the entry's answer
+// steers the descent: FOUND ends the lookup, found below the segment's flushed item upper bound
+// leaves the level (tree/algo/segments.hpp:166-206), anything else goes on.  No path is written
+// and nothing below a hit is visited.  The key is hashed once, before the descent; the ordered
+// form of the query (OrderedQuery) serves the pivots and the leaves.
+constexpr uint32_t kGetThreads = 256;
+// the tile loop's workgroups at most: one round of a full machine (256 CUs x 8 workgroups), as the
+// walk's (tests/test_gpu_get.py sizes the batch that needs a second round from it)
+constexpr uint32_t kGetMaxGrid = 2048;
+
+struct GetArgs : TreeArgs {
+  const uint8_t* filters;
+  const tkv_amq_segment* segs_plan;
+  uint32_t n_plan;
+  uint32_t check_id;
+  const uint8_t* q;
+  const uint64_t* qoffs;
+  uint32_t qstride;
+  uint32_t n_queries;
+  const uint8_t* keys;
+  const uint64_t* koffs;
+  uint32_t kstride;
+  uint32_t n_tiles;
+  uint64_t n_keys;
+  const uint64_t* key_begin;
+  tkv_amq_get_result* result;
+  uint32_t* visits;
+  tkv_amq_probe_metrics* metrics;
+  tkv_amq_get_counts* counts;
+};
+
+// One lane's counts.  Two are not kept, they follow from the others once the wave has summed
+// them: a visit is rejected unless it is one of the other three classes, and a visit that
+// answered "maybe" and is not unsearchable, found or flushed was absent.
+// what a visit came to
+enum GetOutcome : uint32_t { kGetRejected = 0, kGetUnsearchable, kGetAbsent, kGetFlushed, kGetFound };
+
+struct GetTally {
+  uint32_t total = 0, no_filter = 0, mismatch = 0, positive = 0, false_pos = 0;
+  uint32_t found = 0, unsearchable = 0, flushed = 0;
+  // r: result bit | class << 1.  One add per counter, no branch: spelled as increments on the
+  // visit's branches the compiler merged them into one increment through a pointer, and the tally
+  // lived in scratch.
+  __device__ inline void add(uint32_t r, uint32_t outcome)
+  {
+    const uint32_t cls = r >> 1;
+    no_filter += cls == kNoFilter;
+    mismatch += cls == kIdMismatch;
+    positive += r == (1u | (kChecked << 1));
+    false_pos += (cls == kChecked) & (outcome == kGetAbsent);
+    found += outcome == kGetFound;
+    unsearchable += outcome == kGetUnsearchable;
+    flushed += outcome == kGetFlushed;
+  }
+};
+
+__device__ inline void flush_get_tally(const GetTally& t, tkv_amq_probe_metrics* m, tkv_amq_get_counts* c)
+{
+  const uint32_t total = wave_sum(t.total), no_filter = wave_sum(t.no_filter), mismatch = wave_sum(t.mismatch),
+                 positive = wave_sum(t.positive), false_pos = wave_sum(t.false_pos), found = wave_sum(t.found),
+                 unsearchable = wave_sum(t.unsearchable), flushed = wave_sum(t.flushed);
+  if (__lane_id() != 0) return;
+  const uint32_t maybe = no_filter + mismatch + positive;
+  const uint32_t absent = maybe - unsearchable - found - flushed;
+  // one atomic per non-zero counter per wave
+  if (m) {
+    const uint32_t v[6] = {total, no_filter, mismatch, total - maybe, positive, false_pos};
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(m);
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+      if (v[j]) atomicAdd(&d[j], (unsigned long long)v[j]);
+  }
+  if (c) {
+    const uint32_t v[6] = {total, maybe - unsearchable, found, absent, unsearchable, flushed};
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(c);
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+      if (v[j]) atomicAdd(&d[j], (unsigned long long)v[j]);
+  }
+}
+
+// The descent of query i with test(leaf, page id) -> result bit | class << 1 as its filter test.
+template <int ORDER, typename Test>
+__device__ inline void get_one(const GetArgs& a, uint64_t i, GetTally& t, Test&& test)
+{
+  const OrderedQuery<ORDER> q(KeyArray{a.q, a.qoffs, a.qstride}, i);
+  const KeyArray ks{a.keys, a.koffs, a.kstride};
+  uint64_t r_key = ~0ull;
+  uint32_t r_leaf = ~0u, r_where = ~0u, n_visits = 0;
+  // (always inlined, at both of its sites: as a function it would hold the lookup's state on the
+  // stack.  The child leaf's site is where the lanes of a level tree meet again, so the second
+  // copy costs code and no divergence.)
+  auto visit = [&](uint32_t leaf, uint64_t page_id, uint32_t flushed_bound, uint32_t where)
+                   __attribute__((always_inline)) {
+    ++n_visits;
+    // (a leaf outside the plan is "no filter", as load_probe_desc reads it: no segment is loaded)
+    const bool in_plan = leaf < a.n_plan;
+    const uint32_t r = in_plan ? test(leaf, PageIdIs{page_id, a.check_id != 0}) : 1u | (kNoFilter << 1);
+    uint32_t outcome = kGetRejected;
+    if (r & 1u) {
+      outcome = kGetUnsearchable;
+      if (in_plan) {
+        uint64_t b0, e;
+        leaf_key_range(a.key_begin, a.segs_plan, leaf, a.n_keys, b0, e);
+        // the lower bound: lanes with leaves of equal size take the same trip count
+        const uint64_t b = bound(b0, e - b0, [&](uint64_t k) { return q.less(ks, k); });
+        outcome = kGetAbsent;
+        if (b < e && q.equal(ks, b)) {
+          // below the bound the item "has been flushed from this segment": the level is left
+          outcome = b - b0 < flushed_bound ? kGetFlushed : kGetFound;
+          if (outcome == kGetFound) {
+            r_key = b;
+            r_leaf = leaf;
+            r_where = where;
+          }
+        }
+      }
+    }
+    t.add(r, outcome);
+    return outcome == kGetFound ? kWalkStop : outcome == kGetFlushed ? kWalkLeaveLevel : kWalkContinue;
+  };
+  walk_tree(
+      a, [&](uint32_t, uint32_t key_begin, uint32_t pivot_count) { return find_pivot<ORDER>(a, q, key_begin, pivot_count); },
+      [&](uint32_t s, uint32_t p, uint32_t where) {
+        uint32_t leaf, flushed_bound;
+        uint64_t page_id;
+        segment_entry(a, s, p, true, leaf, page_id, flushed_bound);
+        return visit(leaf, page_id, flushed_bound, where);
+      },
+      [&](uint32_t index, uint64_t page_id, uint32_t where) { visit(index, page_id, 0u, where); });
+  t.total += n_visits;
+  *reinterpret_cast<ulonglong2*>(a.result + i) = ulonglong2{r_key, mk64(r_leaf, r_where)};
+  if (a.visits) a.visits[i] = n_visits;
+}
+
+// ORDER: the key order's mode over the three key sides (tkv_amq_key_order.h); HASH: the hash's
+// mode of the query side, as the path probe chooses it.
+template <int KIND, int ORDER, int HASH>
+__device__ inline void get_keys_tiles(const GetArgs& a)
+{
+  // Bloom: the lane's block slot (16-byte keys) or its cache of bit indices (32 bytes and more)
+  __shared__ uint4 s_blk[KIND == TKV_AMQ_BLOOM ? kGetThreads * kProbeSlotWords / 4 : 1];
+  uint4* slot = s_blk + (KIND == TKV_AMQ_BLOOM ? threadIdx.x * (kProbeSlotWords / 4) : 0u);
+  GetTally t;
+  for (uint32_t w = blockIdx.x; w < a.n_tiles; w += gridDim.x) {
+    const uint64_t i = (uint64_t)w * kGetThreads + threadIdx.x;
+    if (i >= a.n_queries) continue;
+    if constexpr (KIND == TKV_AMQ_VQF) {
+      const uint64_t h = vqf_query_hash<HASH>(a.q, a.qoffs, a.qstride, i);
+      get_one<ORDER>(a, i, t, [&](uint32_t leaf, const PageIdIs& id) {
+        return vqf_probe_one<true>(a.filters, a.segs_plan, a.n_plan, leaf, h, id);
+      });
+    } else if constexpr (HASH == kKey16) {
+      const uint4 kv = load_nt16(a.q + 16 * i);
+      const Bloom16 x(kv);
+      const uint64_t h0 = x.h0();
+      const BloomBits16 bits(x);
+      bloom_entry16_park(x, slot);
+      get_one<ORDER>(a, i, t, [&](uint32_t leaf, const PageIdIs& id) {
+        return bloom_entry16_test(h0, bits, bloom_entry16_fetch<true>(a.filters, a.segs_plan, a.n_plan, leaf, h0, id, 0u), slot);
+      });
+    } else {
+      with_bloom_key_at<HASH>(a.q, a.qoffs, a.qstride, i, [&](const auto& x) {
+        const uint64_t h0 = x.h0();
+        BloomBitSource<std::decay_t<decltype(x)>> bit_of{x, reinterpret_cast<uint16_t*>(slot)};
+        get_one<ORDER>(a, i, t, [&](uint32_t leaf, const PageIdIs& id) {
+          return bloom_entry_test<true>(a.filters, a.segs_plan, a.n_plan, leaf, h0, id, 0u, bit_of);
+        });
+      });
+    }
+  }
+  flush_get_tally(t, a.metrics, a.counts);
+}
+
+// Occupancy: every step of a lookup is a dependent read, so the throughput comes from waves in
+// flight, and the lane holds the hash state, the ordered query, the descent and eight tallies:
+// 96-140 VGPRs, 3-5 waves per SIMD, no scratch.  No form asks for more
+// waves: the compiler would meet the request by spilling registers to scratch.
+template <int KIND, int ORDER, int HASH>
+__global__ __launch_bounds__(kGetThreads) void get_keys_kernel(GetArgs a)
+{
+  get_keys_tiles<KIND, ORDER, HASH>(a);
 }
 
 __global__ __launch_bounds__(256) void gen_keys16_kernel(uint64_t seed, uint64_t first, uint64_t n,
@@ -7351,6 +7550,97 @@ int tkv_amq_path_probe(int kind, const uint8_t* d_filters, const tkv_amq_segment
   hipLaunchKernelGGL(scan_totals<uint32_t>, dim3(1), dim3(256), 0, s, a.wg_total, a.n_wgs,
                      d_cand_begin + a.n_queries, a.n_entries, static_cast<uint64_t*>(nullptr));
   hipLaunchKernelGGL(path_scatter, dim3(a.n_wgs), block, 0, s, a);
+  return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
+}
+
+int tkv_amq_get_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs, uint32_t n_segs,
+                     const tkv_amq_tree_node* nodes, uint64_t n_nodes, const tkv_amq_tree_segment* segments,
+                     uint64_t n_segments, const tkv_amq_tree_child* children, uint64_t n_children,
+                     const uint32_t* d_flushed_bounds, uint64_t n_flushed_bounds, const uint8_t* pivot_keys,
+                     const uint64_t* pivot_key_offsets, uint32_t pivot_key_stride, uint64_t n_pivot_keys,
+                     const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
+                     uint64_t n_queries, const uint8_t* leaf_keys, const uint64_t* leaf_key_offsets,
+                     uint32_t leaf_key_stride, uint64_t n_leaf_keys, const uint64_t* d_key_begin, uint32_t flags,
+                     tkv_amq_get_result* d_result, uint32_t* d_query_visits, tkv_amq_probe_metrics* d_metrics,
+                     tkv_amq_get_counts* d_counts, void* stream)
+{
+  // (the arguments are judged first, so a bad call is InvalidArgument with or without a device)
+  constexpr uint64_t kMax = 0xffffffffull;
+  if (kind != TKV_AMQ_BLOOM && kind != TKV_AMQ_VQF) return TKV_AMQ_INVALID_ARGUMENT;
+  if (flags & ~TKV_AMQ_GET_CHECK_PAGE_ID) return TKV_AMQ_INVALID_ARGUMENT;
+  if (n_nodes > kMax || n_segments > kMax || n_children > kMax || n_flushed_bounds > kMax ||
+      n_pivot_keys > kMax || n_queries > kMax)
+    return TKV_AMQ_INVALID_ARGUMENT;
+  if ((n_nodes && !nodes) || (n_segments && !segments) || (n_children && !children) ||
+      (n_flushed_bounds && !d_flushed_bounds) || (n_pivot_keys && !pivot_keys) || (n_leaf_keys && !leaf_keys))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  if (n_segs && (!d_segs || !d_filters)) return TKV_AMQ_INVALID_ARGUMENT;
+  if (n_queries && (!queries || !d_result)) return TKV_AMQ_INVALID_ARGUMENT;
+  if ((!pivot_key_offsets && !pivot_key_stride) || (!query_offsets && !query_stride) ||
+      (!leaf_key_offsets && !leaf_key_stride))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  if (((reinterpret_cast<uintptr_t>(nodes) | reinterpret_cast<uintptr_t>(segments) |
+        reinterpret_cast<uintptr_t>(children) | reinterpret_cast<uintptr_t>(d_result)) & 15) ||
+      ((reinterpret_cast<uintptr_t>(d_metrics) | reinterpret_cast<uintptr_t>(d_counts)) & 7) ||
+      (reinterpret_cast<uintptr_t>(d_query_visits) & 3))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  // the hash's mode is the path probe's, with its rule for 16-byte queries
+  const int hash_mode = key_mode(query_offsets, query_stride);
+  if (hash_mode == kKey16 && (reinterpret_cast<uintptr_t>(queries) & 15)) return TKV_AMQ_INVALID_ARGUMENT;
+  if (tkv_amq_device_count() == 0) return TKV_AMQ_UNAVAILABLE;
+  if (n_queries == 0) return TKV_AMQ_OK;
+  GetArgs a;
+  a.nodes = nodes;
+  a.segs = segments;
+  a.children = children;
+  a.bounds = d_flushed_bounds;
+  a.n_nodes = (uint32_t)n_nodes;
+  a.n_segs = (uint32_t)n_segments;
+  a.n_children = (uint32_t)n_children;
+  a.n_bounds = (uint32_t)n_flushed_bounds;
+  a.pk = pivot_keys;
+  a.pkoffs = pivot_key_offsets;
+  a.pkstride = pivot_key_stride;
+  a.n_pk = (uint32_t)n_pivot_keys;
+  a.filters = d_filters;
+  a.segs_plan = d_segs;
+  a.n_plan = n_segs;
+  a.check_id = (flags & TKV_AMQ_GET_CHECK_PAGE_ID) ? 1u : 0u;
+  a.q = queries;
+  a.qoffs = query_offsets;
+  a.qstride = query_stride;
+  a.n_queries = (uint32_t)n_queries;
+  a.keys = leaf_keys;
+  a.koffs = leaf_key_offsets;
+  a.kstride = leaf_key_stride;
+  a.n_tiles = (uint32_t)div_up(n_queries, kGetThreads);
+  a.n_keys = n_leaf_keys;
+  a.key_begin = d_key_begin;
+  a.result = d_result;
+  a.visits = d_query_visits;
+  a.metrics = d_metrics;
+  a.counts = d_counts;
+  // one order for the pivots and the leaves: a fast mode only if all three sides have its shape
+  const KeyArray qa{queries, query_offsets, query_stride};
+  const int op = key_order_mode(qa, KeyArray{pivot_keys, pivot_key_offsets, pivot_key_stride});
+  const int ol = key_order_mode(qa, KeyArray{leaf_keys, leaf_key_offsets, leaf_key_stride});
+  const int order = op == ol ? op : (int)kOrderAny;
+  const dim3 grid(a.n_tiles < kGetMaxGrid ? a.n_tiles : kGetMaxGrid), block(kGetThreads);
+  const hipStream_t s = as_stream(stream);
+  auto launch = [&](auto K) {
+    constexpr int KIND = decltype(K)::value;
+    if (order == kOrder16) {
+      hipLaunchKernelGGL((get_keys_kernel<KIND, kOrder16, kKey16>), grid, block, 0, s, a);
+    } else if (order == kOrder24) {
+      hipLaunchKernelGGL((get_keys_kernel<KIND, kOrder24, kKeyFixed>), grid, block, 0, s, a);
+    } else {
+      with_key_mode(hash_mode, [&](auto M) {
+        hipLaunchKernelGGL((get_keys_kernel<KIND, kOrderAny, decltype(M)::value>), grid, block, 0, s, a);
+      });
+    }
+  };
+  if (kind == TKV_AMQ_BLOOM) launch(KeyModeC<TKV_AMQ_BLOOM>{});
+  else launch(KeyModeC<TKV_AMQ_VQF>{});
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
 

@@ -13,11 +13,12 @@
 //   walk_write_kernel  the same descent with the pivots read back: no key is compared again, only
 //                      nodes, bit sets and children are re-read; entries go to their positions.
 //
-// Both descents are one function (walk_tree) with the pivot source and the entry sink as
-// arguments, so the two passes cannot disagree about a path.  A tree over thousands of leaves is
-// about a hundred nodes: it stays in L2, every step is a dependent L2 read, and the throughput
-// comes from waves in flight.  Every index is checked against its array
-// before the read, so a malformed tree gives a defined answer.
+// Both descents are one function (walk_tree, tkv_amq_tree_walk.h: shared with tkv_amq_get_keys) with
+// the pivot source and the entry sink as arguments, so the two passes cannot disagree about a
+// path.  A tree over thousands of leaves is about a hundred nodes: it stays in L2, every step is
+// a dependent L2 read, and the throughput comes from waves in flight.
+// Every index is checked against its array before the read, so a malformed tree gives a defined
+// answer.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -25,6 +26,7 @@
 #include "tkv_amq.h"
 #include "tkv_amq_device.h"
 #include "tkv_amq_scan.h"
+#include "tkv_amq_tree_walk.h"
 
 namespace tkv {
 namespace {
@@ -37,23 +39,12 @@ constexpr uint32_t kWalkMaxGrid = 2048;
 constexpr uint32_t kWalkScanPerThread = 4;
 constexpr uint32_t kWalkTrailSplit = 10;  // depths 0..9 in the trail's low word, 10..15 in the high
 
-static_assert(sizeof(tkv_amq_tree_node) == 32 && sizeof(tkv_amq_tree_segment) == 32 &&
-                  sizeof(tkv_amq_tree_child) == 16,
-              "tree records");
 static_assert(kWalkThreads == kBlockScanThreads && kWalkScanPerThread == kScanTotalsPerThread,
               "a tile is one block scan; scan_totals' span");
 static_assert(TKV_AMQ_WALK_MAX_DEPTH == 16, "the trail holds 16 pivots of 6 bits");
 
-struct WalkArgs {
-  const tkv_amq_tree_node* nodes;
-  const tkv_amq_tree_segment* segs;
-  const tkv_amq_tree_child* children;
-  const uint32_t* bounds;
-  uint32_t n_nodes, n_segs, n_children, n_bounds;
-  const uint8_t* pk;
-  const uint64_t* pkoffs;
-  uint32_t pkstride;
-  uint32_t n_pk;
+// (the tree, TreeArgs, comes first: the layout the kernels had before the descent was shared)
+struct WalkArgs : TreeArgs {
   const uint8_t* q;
   const uint64_t* qoffs;
   uint32_t qstride;
@@ -70,22 +61,6 @@ struct WalkArgs {
   uint64_t* tile_total;  // [n_tiles]: totals, then their exclusive prefixes
 };
 
-// The pivot of the query in a node that owns keys k0..kp from `key_begin`: the number of interior
-// keys k1..k(p-1) that are <= the query (std::upper_bound over them).  k0 and kp are never read;
-// interior keys at or past n_pk do not exist.
-template <int MODE>
-__device__ inline uint32_t find_pivot(const WalkArgs& a, const OrderedQuery<MODE>& q, uint32_t key_begin,
-                                      uint32_t pivot_count)
-{
-  const uint64_t first = (uint64_t)key_begin + 1;
-  const uint64_t have = first < a.n_pk ? a.n_pk - first : 0;
-  uint32_t len = pivot_count - 1;
-  len = have < len ? (uint32_t)have : len;
-  // lanes in nodes of equal fan-out take the same trip count (at most 6)
-  const KeyArray pk{a.pk, a.pkoffs, a.pkstride};
-  return (uint32_t)(bound(first, len, [&](uint64_t k) { return q.less_equal(pk, k); }) - first);
-}
-
 // The pivots of one walk, 6 bits per depth.
 struct Trail {
   uint64_t lo = 0, hi = 0;
@@ -100,41 +75,6 @@ struct Trail {
     return (uint32_t)w & 63u;
   }
 };
-
-// One query's descent.  pivot(depth, key_begin, pivot_count) names the pivot; entry(seg index, p,
-// where) is called for every segment active for it, leaf(index, page id, where) for the child leaf.
-template <class Pivot, class Entry, class Leaf>
-__device__ inline void walk_tree(const WalkArgs& a, Pivot&& pivot, Entry&& entry, Leaf&& leaf)
-{
-  uint32_t ni = 0;
-  for (uint32_t depth = 0; depth < TKV_AMQ_WALK_MAX_DEPTH; ++depth) {
-    if (ni >= a.n_nodes) return;
-    const uint4* np = reinterpret_cast<const uint4*>(a.nodes + ni);
-    const uint4 n0 = np[0], n1 = np[1];  // {pivot_key_begin, seg_begin, child_begin, -}, {counts, level_start, -}
-    const uint32_t pivot_count = n1.x & 0xffu, height = (n1.x >> 8) & 0xffu;
-    const uint32_t level_count = min((n1.x >> 16) & 0xffu, 7u);
-    if (pivot_count == 0 || pivot_count > 64) return;
-    const uint32_t p = pivot(depth, n0.x, pivot_count);
-    const uint64_t bit = 1ull << p;
-    const uint64_t level_start = mk64(n1.y, n1.z);
-    for (uint32_t l = 0; l < level_count; ++l) {
-      // (64-bit sums cannot wrap; a decreasing level_start gives end <= begin: an empty level)
-      const uint64_t lb = (uint64_t)n0.y + ((level_start >> (8 * l)) & 0xffu);
-      const uint64_t le = (uint64_t)n0.y + ((level_start >> (8 * l + 8)) & 0xffu);
-      const uint32_t sb = (uint32_t)min(lb, (uint64_t)a.n_segs), se = (uint32_t)min(le, (uint64_t)a.n_segs);
-      for (uint32_t s = sb; s < se; ++s)
-        if (a.segs[s].active_pivots & bit) entry(s, p, (depth << 8) | l);
-    }
-    const uint64_t c = (uint64_t)n0.z + p;
-    if (c >= a.n_children) return;
-    const uint4 ch = *reinterpret_cast<const uint4*>(a.children + c);  // {page_id, index, -}
-    if (height <= 1) {
-      leaf(ch.z, mk64(ch.x, ch.y), (depth << 8) | TKV_AMQ_WALK_LEAF_LEVEL);
-      return;
-    }
-    ni = ch.z;
-  }
-}
 
 // exclusive scan of v over the workgroup's 256 threads; *total = the sum.  s: 4 words of LDS.
 // The scheme of block_exclusive_scan (tkv_amq_scan.h) with the barriers placed differently.  Kept
@@ -181,7 +121,11 @@ __global__ __launch_bounds__(kWalkThreads) void walk_count_kernel(WalkArgs a)
             trail.put(depth, p);
             return p;
           },
-          [&](uint32_t, uint32_t, uint32_t) { ++cnt; }, [&](uint32_t, uint64_t, uint32_t) { ++cnt; });
+          [&](uint32_t, uint32_t, uint32_t) {
+            ++cnt;
+            return kWalkContinue;
+          },
+          [&](uint32_t, uint64_t, uint32_t) { ++cnt; });
       a.trail[i] = ulonglong2{trail.lo, trail.hi};
     }
     uint32_t total;
@@ -215,16 +159,11 @@ __global__ __launch_bounds__(kWalkThreads) void walk_write_kernel(WalkArgs a)
     walk_tree(
         a, [&](uint32_t depth, uint32_t, uint32_t) { return trail.get(depth); },
         [&](uint32_t s, uint32_t p, uint32_t where) {
-          const uint4* sp = reinterpret_cast<const uint4*>(a.segs + s);
-          const uint4 s0 = sp[0], s1 = sp[1];  // {leaf_page_id, active}, {flushed, leaf, flushed_begin}
-          const uint64_t flushed = mk64(s1.x, s1.y);
-          uint32_t bound = 0;
-          if (a.path_flushed && ((flushed >> p) & 1u)) {
-            // bit_rank: the set bits of flushed_pivots below p
-            const uint64_t at = (uint64_t)s1.w + (uint32_t)__popcll(flushed & ((1ull << p) - 1));
-            if (at < a.n_bounds) bound = a.bounds[at];
-          }
-          put(s1.z, mk64(s0.x, s0.y), bound, where);
+          uint32_t leaf, bound;
+          uint64_t page_id;
+          segment_entry(a, s, p, a.path_flushed != nullptr, leaf, page_id, bound);
+          put(leaf, page_id, bound, where);
+          return kWalkContinue;
         },
         [&](uint32_t index, uint64_t page_id, uint32_t where) { put(index, page_id, 0u, where); });
   }

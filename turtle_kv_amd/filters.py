@@ -1281,6 +1281,103 @@ def walk_paths(tree: TreeIndex, queries: KeyBatch, capacity: int | None = None, 
                       None if where is None else where[:capacity], needed, capacity, workspace)
 
 # ---------------------------------------------------------------------------------------
+# fused point lookup: root to found key in one launch
+# ---------------------------------------------------------------------------------------
+class GetCounts:
+    """Device-side tkv_amq_get_counts that get_keys launches add to; `collect()` reads them."""
+
+    def __init__(self, device=None):
+        torch = _torch()
+        self.counts = torch.zeros(len(abi.GET_COUNTS_FIELDS), dtype=torch.int64, device=device or "cuda")
+
+    def reset(self) -> None:
+        self.counts.zero_()
+
+    def collect(self) -> dict:
+        return dict(zip(abi.GET_COUNTS_FIELDS, (int(v) for v in self.counts.cpu().tolist())))
+
+
+@dataclass
+class GetResult:
+    """What get_keys leaves on the device, per query: the global index (into the leaf keys) of the
+    found key (-1, i.e. abi.NOT_FOUND as int64, if none), the leaf that holds it (-1 if none) and
+    `where`, depth << 8 | level of the entry that held it (level abi.WALK_LEAF_LEVEL: the child
+    leaf; -1 if none); `visits`: the number of entries the lookup visited, if asked for.  `raw` is
+    the tkv_amq_get_result array itself (uint8 [16 * n_queries], abi.GET_RESULT_DTYPE records);
+    the three fields are views into it."""
+    key_index: object                    # int64 [n_queries]
+    leaf: object                         # int32 [n_queries]
+    where: object                        # int32 [n_queries]
+    visits: object = None                # int32 [n_queries], or None
+    raw: object = field(default=None, repr=False)
+
+
+def get_keys_device(kind: int, filters, d_segs, n_segs: int, d_nodes, n_nodes: int, d_segments,
+                    n_segments: int, d_children, n_children: int, d_flushed_bounds, n_flushed_bounds: int,
+                    pivot_keys, pivot_key_offsets, pivot_key_stride: int, n_pivot_keys: int, queries,
+                    query_offsets, query_stride: int, n_queries: int, leaf_keys, leaf_key_offsets,
+                    leaf_key_stride: int, n_leaf_keys: int, d_key_begin, d_result, d_query_visits=None,
+                    flags: int = 0, d_metrics=None, d_counts=None, stream=None) -> None:
+    """The launch alone (tkv_amq_get_keys), capturable: raw device tensors in, nothing allocated,
+    nothing copied back.  The tree as walk_paths_device takes it, the leaf keys as find_keys_device
+    takes them; d_result: uint8 [16 * n_queries] (abi.GET_RESULT_DTYPE records); d_query_visits:
+    int32 [n_queries] or None; d_metrics: int64 [6] (ProbeMetrics.counts) or None; d_counts: int64
+    [6] (GetCounts.counts) or None."""
+    _require_device()
+    st = abi.lib().tkv_amq_get_keys(
+        kind, _ptr(filters), _ptr(d_segs), int(n_segs), _ptr(d_nodes), int(n_nodes), _ptr(d_segments),
+        int(n_segments), _ptr(d_children), int(n_children), _ptr(d_flushed_bounds), int(n_flushed_bounds),
+        _ptr(pivot_keys), _ptr(pivot_key_offsets), int(pivot_key_stride), int(n_pivot_keys), _ptr(queries),
+        _ptr(query_offsets), int(query_stride), int(n_queries), _ptr(leaf_keys), _ptr(leaf_key_offsets),
+        int(leaf_key_stride), int(n_leaf_keys), _ptr(d_key_begin), int(flags), _ptr(d_result),
+        _ptr(d_query_visits), _ptr(d_metrics), _ptr(d_counts), _stream_handle(stream))
+    abi.check(st, "tkv_amq_get_keys")
+
+
+def get_keys(plan_or_opened, filters, tree: TreeIndex, queries: KeyBatch, leaf_keys: KeyBatch, *,
+             key_begin=None, check_page_ids: bool = False, want_visits: bool = False,
+             metrics: ProbeMetrics | None = None, counts: GetCounts | None = None,
+             stream=None) -> GetResult:
+    """A batch of point lookups in one launch (tkv_amq_get_keys): each query descends `tree`, asks
+    the filter of every entry on its way (hashed once), searches the leaves whose filters say
+    maybe, and ends at the first leaf that holds its key -- skipping the rest of a level when the
+    key is found below the segment's flushed item upper bound, as the reference does.  What
+    walk_paths -> probe_paths -> find_keys compute for a tree without flushed bounds, without a
+    path in memory and without a visit below the hit.  Leaf s holds leaf_keys [key_begin[s],
+    key_begin[s+1]) or, without key_begin, the plan's own range, in ascending byte order.
+    check_page_ids: a filter whose stored page id differs from the tree's id of the leaf cannot
+    reject.  `metrics` takes KeyQuery::Metrics (the false positives included), `counts` the
+    lookup's own tallies.  Nothing is copied back: the result stays on the device."""
+    torch = _torch()
+    _require_device()
+    plan = plan_or_opened.plan if isinstance(plan_or_opened, OpenedFilters) else plan_or_opened
+    dev = queries.data.device
+    n = plan.n_segs
+    d_kb = None
+    if key_begin is not None:
+        d_kb = (key_begin if hasattr(key_begin, "data_ptr") else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(key_begin, dtype=np.uint64)).view(np.int64))).to(
+                device=dev, dtype=torch.int64).contiguous()
+        if int(d_kb.numel()) != n + 1:
+            raise TkvAmqError(abi.INVALID_ARGUMENT, "get_keys: key_begin needs n_segs + 1 entries")
+    d_nodes, d_segments, d_kids, d_bounds, pk = tree.device(dev)
+    raw = torch.empty(max(queries.n, 1) * 16, dtype=torch.uint8, device=dev)
+    visits = torch.empty(max(queries.n, 1), dtype=torch.int32, device=dev) if want_visits else None
+    get_keys_device(plan.kind, filters if n else None, plan.device_segs(dev) if n else None, n, d_nodes,
+                    len(tree.nodes), d_segments, len(tree.segments), d_kids, len(tree.children), d_bounds,
+                    len(tree.flushed_bounds), pk.data, pk.offsets, pk.stride, pk.n, queries.data,
+                    queries.offsets, queries.stride, queries.n, leaf_keys.data, leaf_keys.offsets,
+                    leaf_keys.stride, leaf_keys.n, d_kb, raw, visits,
+                    abi.GET_CHECK_PAGE_ID if check_page_ids else 0,
+                    None if metrics is None else metrics.counts, None if counts is None else counts.counts,
+                    stream)
+    _hold(stream, d_kb, raw, visits)
+    rec = raw[:16 * queries.n].view(torch.int64).view(queries.n, 2)
+    lc = raw[:16 * queries.n].view(torch.int32).view(queries.n, 4)
+    return GetResult(rec[:, 0], lc[:, 2], lc[:, 3], None if visits is None else visits[:queries.n], raw)
+
+
+# ---------------------------------------------------------------------------------------
 # single-leaf API (the reference's per-leaf entry points)
 # ---------------------------------------------------------------------------------------
 @dataclass
