@@ -72,6 +72,21 @@ class World:
         self.n = len(counts)
         self._answers = {}
 
+    @classmethod
+    def over(cls, oracle, plan, leaves, payload):
+        """The same over filters that no one plan built and nothing here builds: `plan` holds their
+        segments (an opened array's: hash counts, tag widths and page ids per segment; a segment
+        without a filter where a slot was refused), payload[s] the bytes of segment s.  Host only:
+        `filt`, `leaf_kb` and the device's own copy of the plan are the caller's to attach."""
+        w = cls.__new__(cls)
+        w.oracle, w.kind, w.leaves = oracle, plan.kind, [list(lv) for lv in leaves]
+        assert all(lv == sorted(set(lv)) for lv in w.leaves) and len(w.leaves) == plan.n_segs == len(payload)
+        w.begin = np.concatenate([[0], np.cumsum([len(lv) for lv in w.leaves])]).astype(np.int64)
+        w.src = plan.segs["src_page_id"].astype(np.uint64)
+        w.plan, w.payload, w.n, w._answers = plan, list(payload), plan.n_segs, {}
+        w.filt = w.leaf_kb = None
+        return w
+
     def ask(self, leaf_i, page_id, key, check_ids):
         """(class, answer) of one visit, as reject_page classifies it."""
         if leaf_i >= self.n:

@@ -45,13 +45,17 @@ def dev(torch, a):
 # ---------------------------------------------------------------------------------------
 # expectations: the oracle's answer per (query, leaf), then the probes' classes on top of it
 # ---------------------------------------------------------------------------------------
-def expected(plan, seg, ref, page_ids=None, truth=None):
+def expected(plan, seg, ref, page_ids=None, truth=None, k_max=None):
     """(answers, the six counters) of pairs asking leaf seg[i], as expected_metrics of
     test_gpu_pages_metrics.py derives them.  ref[i]: the oracle's answer for pair i on leaf
-    min(seg[i], n_segs - 1) (unused where the leaf is outside the plan)."""
+    min(seg[i], n_segs - 1) (unused where the leaf is outside the plan or has no filter).  k_max:
+    the hashed Bloom probe's record holds k_max hashes, and a filter of more is "no filter" to it
+    (include/tkv_amq.h) -- segment by segment, before the page-id check."""
     n = plan.n_segs
     sc = np.minimum(seg, n - 1)
     built = plan.segs["hash_count" if plan.kind == BLOOM else "tag_bits"] != 0
+    if k_max is not None and plan.kind == BLOOM:
+        built = built & (plan.segs["hash_count"] <= k_max)
     has = (seg < n) & built[sc]
     mism = np.zeros(len(seg), bool) if page_ids is None else has & (plan.segs["src_page_id"][sc] != page_ids)
     checked = has & ~mism
@@ -62,10 +66,13 @@ def expected(plan, seg, ref, page_ids=None, truth=None):
 
 
 def table16(oracle, plan, host, q16):
-    """oracle.probe_segments of every 16-byte query on every leaf of the plan: [n_queries, n_segs]."""
-    t = np.empty((len(q16), plan.n_segs), np.uint8)
+    """oracle.probe_segments of every 16-byte query on every leaf of the plan: [n_queries, n_segs].
+    The column of a "no filter" segment (an opened plan's refused slot: the oracle has nothing to
+    read there) is 1 and unused by `expected`."""
+    t = np.ones((len(q16), plan.n_segs), np.uint8)
     q16 = np.ascontiguousarray(q16)
-    for s in range(plan.n_segs):
+    built = plan.segs["hash_count" if plan.kind == BLOOM else "tag_bits"] != 0
+    for s in np.flatnonzero(built):
         st, r = oracle.probe_segments(plan.kind, host, plan.segs["out_offset"], q16,
                                       np.full(len(q16), s, np.uint32))
         assert st == 0
@@ -89,28 +96,34 @@ class Routes:
         self.__dict__.update(kw)
 
 
-def make_routes(rng, plan, table, seg, leaf_draw, long_at):
+def make_routes(rng, plan, table, seg, leaf_draw, long_at, fixed_paths=None):
+    """fixed_paths: {query: its path's leaves, in entry order}, in place of the random path."""
     r, n, nq = Routes(), plan.n_segs, len(seg)
     look = lambda qi, s: table[qi, np.minimum(s, n - 1)]
     r.nq, r.seg = nq, seg
     # one leaf per query: the plain probe, the probe with options, the hashed probe
     r.page_ids, r.truth = options_for(rng, plan, seg)
-    ref = look(np.arange(nq), seg)
+    r.ref = ref = look(np.arange(nq), seg)
     r.plain = expected(plan, seg, ref)
     r.opts = expected(plan, seg, ref, r.page_ids, r.truth)
     r.share = float(ref[seg < n].mean())
     # (query, leaf) pairs through pair_query
     r.pair_query, r.pair_seg = rng.integers(0, nq, nq), leaf_draw(nq)
     r.pair_page_ids, r.pair_truth = options_for(rng, plan, r.pair_seg)
-    ref = look(r.pair_query, r.pair_seg)
+    r.pair_ref = ref = look(r.pair_query, r.pair_seg)
     r.pair_plain = expected(plan, r.pair_seg, ref)
     r.pair_opts = expected(plan, r.pair_seg, ref, r.pair_page_ids, r.pair_truth)
     # paths of 0 .. 3 entries, and one of 40: past kPathMaskEntries (32), whose answers are bytes
     lens = rng.integers(0, 4, nq)
     lens[long_at] = 40
+    for qi, leaves in (fixed_paths or {}).items():
+        assert qi != long_at
+        lens[qi] = len(leaves)
     r.path_begin = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     r.n_entries = int(r.path_begin[-1])
     r.path_leaf = leaf_draw(r.n_entries).astype(np.int64)
+    for qi, leaves in (fixed_paths or {}).items():
+        r.path_leaf[r.path_begin[qi]:r.path_begin[qi + 1]] = leaves
     r.path_query, r.path_entry, _ = expand(r.path_begin, r.n_entries)
     r.path_page_ids, r.path_truth = options_for(rng, plan, r.path_leaf)
     ref = look(r.path_query, r.path_leaf)
@@ -163,45 +176,63 @@ def hashed_call(amq, plan, filt, hashes, k_max, d_seg, **kw):
     return amq.bloom_probe_hashed(plan, filt, hashes, k_max, d_seg, **kw)
 
 
+def hashed_expected(plan, r, k_max):
+    """The four expectations of the hashed probe whose records hold k_max hashes: r's own where no
+    filter of the plan has more (every VQF plan; k_max None), else `expected` over the same
+    oracle answers with the longer filters classed as the header classes them."""
+    if plan.kind == VQF or k_max is None or int(plan.segs["hash_count"].max()) <= k_max:
+        return r.plain, r.pair_plain, r.opts, r.pair_opts
+    return (expected(plan, r.seg, r.ref, k_max=k_max), expected(plan, r.pair_seg, r.pair_ref, k_max=k_max),
+            expected(plan, r.seg, r.ref, r.page_ids, r.truth, k_max=k_max),
+            expected(plan, r.pair_seg, r.pair_ref, r.pair_page_ids, r.pair_truth, k_max=k_max))
+
+
 def check_hashed(amq, torch, plan, filt, qb, r, k_maxes=(None,)):
     d_seg, d_ps = dev(torch, r.seg.astype(np.int32)), dev(torch, r.pair_seg.astype(np.int32))
     d_pq = dev(torch, r.pair_query.astype(np.int32))
     for k_max in k_maxes:
+        plain, pair_plain, opts, pair_opts = hashed_expected(plan, r, k_max)
         h = amq.vqf_hash_val(qb) if plan.kind == VQF else amq.bloom_query_hashes(qb, k_max)
         res = hashed_call(amq, plan, filt, h, k_max, d_seg)
-        assert np.array_equal(res.cpu().numpy(), r.plain[0]), k_max
+        assert np.array_equal(res.cpu().numpy(), plain[0]), k_max
         res = hashed_call(amq, plan, filt, h, k_max, d_ps, pair_query=d_pq)
-        assert np.array_equal(res.cpu().numpy(), r.pair_plain[0]), k_max
+        assert np.array_equal(res.cpu().numpy(), pair_plain[0]), k_max
         pm = amq.ProbeMetrics()
         res = hashed_call(amq, plan, filt, h, k_max, d_seg, query_page_ids=ids(torch, r.page_ids),
                           truth=dev(torch, r.truth), metrics=pm)
-        assert np.array_equal(res.cpu().numpy(), r.opts[0]), k_max
-        assert pm.collect() == r.opts[1], k_max
+        assert np.array_equal(res.cpu().numpy(), opts[0]), k_max
+        assert pm.collect() == opts[1], k_max
         pm = amq.ProbeMetrics()
         res = hashed_call(amq, plan, filt, h, k_max, d_ps, pair_query=d_pq,
                           query_page_ids=ids(torch, r.pair_page_ids), truth=dev(torch, r.pair_truth), metrics=pm)
-        assert np.array_equal(res.cpu().numpy(), r.pair_opts[0]), k_max
-        assert pm.collect() == r.pair_opts[1], k_max
+        assert np.array_equal(res.cpu().numpy(), pair_opts[0]), k_max
+        assert pm.collect() == pair_opts[1], k_max
 
 
 def check_k_max_below(amq, torch, plan, filt, qb, r, k_max):
-    """Every filter of the plan has more hashes than the cache holds: no pair can be rejected,
-    and each counts as no_filter_page_count (include/tkv_amq.h) -- before the page-id check."""
+    """Filters of the plan have more hashes than the cache holds: a pair on one of them cannot be
+    rejected and counts as no_filter_page_count (include/tkv_amq.h) -- before the page-id check;
+    every other pair is tested as usual.  Into zeroed results, so an answer 1 was written."""
     h = amq.bloom_query_hashes(qb, k_max)
-    none = dict(zip(FIELDS, (r.nq, r.nq, 0, 0, 0, 0)))
-    for seg, pq, page_ids, truth in ((r.seg, None, r.page_ids, r.truth),
-                                     (r.pair_seg, r.pair_query, r.pair_page_ids, r.pair_truth)):
+    plain, pair_plain, opts, pair_opts = hashed_expected(plan, r, k_max)
+    if (plan.segs["hash_count"] > k_max).all():     # no filter can be asked: every pair is of that class
+        none = dict(zip(FIELDS, (r.nq, r.nq, 0, 0, 0, 0)))
+        for ans, m in (plain, pair_plain, opts, pair_opts):
+            assert ans.all() and m == none
+    for seg, pq, page_ids, truth, want, want_opts in (
+            (r.seg, None, r.page_ids, r.truth, plain, opts),
+            (r.pair_seg, r.pair_query, r.pair_page_ids, r.pair_truth, pair_plain, pair_opts)):
         d_seg = dev(torch, seg.astype(np.int32))
         d_pq = None if pq is None else dev(torch, pq.astype(np.int32))
         out = torch.zeros(r.nq, dtype=torch.uint8, device="cuda")
         amq.bloom_probe_hashed(plan, filt, h, k_max, d_seg, out=out, pair_query=d_pq)
-        assert bool(out.all())
+        assert np.array_equal(out.cpu().numpy(), want[0])
         out.zero_()
         pm = amq.ProbeMetrics()
         amq.bloom_probe_hashed(plan, filt, h, k_max, d_seg, out=out, pair_query=d_pq,
                                query_page_ids=ids(torch, page_ids), truth=dev(torch, truth), metrics=pm)
-        assert bool(out.all())
-        assert pm.collect() == none
+        assert np.array_equal(out.cpu().numpy(), want_opts[0])
+        assert pm.collect() == want_opts[1]
 
 
 def check_paths(amq, torch, plan, filt, qb, r):
@@ -217,13 +248,14 @@ def check_paths(amq, torch, plan, filt, qb, r):
     assert pm.collect() == r.path_opts[1]
 
 
-def check_verify(amq, torch, plan, filt, vkb, r):
+def check_verify(amq, torch, plan, filt, vkb, r, hints=("plan", 1), flags=0):
     """max_seg_blocks as planned: the leaf's image in LDS; 1: every leaf of more than one block is
-    read from global memory."""
+    read from global memory; a hint between: the leaves above it alone.  flags: per leaf, where
+    the plan holds a "no filter" segment."""
     assert plan.max_seg_blocks > 1
-    for hint in ("plan", 1):
+    for hint in hints:
         res, total = verify_run(amq, torch, plan, filt, vkb, key_begin=r.v_begin, hint=hint)
-        assert_result(res, total, r.v_missing, r.v_first, flags=0)
+        assert_result(res, total, r.v_missing, r.v_first, flags=flags)
 
 
 def assert_built_as_oracle(amq, torch, plan, keys, host):
