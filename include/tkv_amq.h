@@ -53,12 +53,21 @@
  *                           tree/algo/segmented_levels.hpp:340-369): each lookup's ordered list of
  *                           leaves, with page ids, flushed item upper bounds (packed_node_page.cpp:
  *                           231-248) and (depth, level) per entry
- *   tkv_amq_get_keys        the three above in one call and in the reference's order: the whole
- *                           point lookup (NodeAlgorithms::find_key, tree/algo/nodes.hpp:158-187) with
- *                           both of its stopping rules -- the first level that yields the key ends
- *                           it, and an item found below a segment's flushed item upper bound
- *                           (SegmentAlgorithms::find_key, tree/algo/segments.hpp:166-206) leaves the
- *                           level -- and KeyQuery::Metrics over the filters the reference asks
+ *   tkv_amq_get_keys        the three above in one call and in the reference's order: the point
+ *                           lookup (NodeAlgorithms::find_key, tree/algo/nodes.hpp:158-187) for values
+ *                           that need no combining, with two of its stopping rules -- the first
+ *                           level that yields the key ends it, and an item found below a segment's
+ *                           flushed item upper bound (SegmentAlgorithms::find_key, tree/algo/
+ *                           segments.hpp:166-206) leaves the level -- and KeyQuery::Metrics over the
+ *                           filters the reference asks
+ *   tkv_amq_get_values      the same lookup with find_key's third rule, the value rule: each found
+ *                           item's packed value (unpack_value_view, core/packed_key_value.hpp:18-23:
+ *                           an op byte, then the data) is folded into the lookup's value as
+ *                           combine_in_place folds it (core/value_view.hpp:316-361), and the lookup
+ *                           goes on through older levels and the child while the value
+ *                           needs_combine() (:279-285) -- OP_ADD_I32 deltas are summed until an
+ *                           OP_WRITE or an OP_DELETE resolves them
+ *   tkv_amq_gather_values   the resolved values' bytes, one fixed slot per lookup
  *   tkv_amq_open_filters    what KeyQuery::reject_page reads from a loaded filter page instead
  *                           of a plan (tree/key_query.hpp:149-247): check_magic()
  *                           (vqf_filter_page_view.hpp:96-100), src_page_id, block_count,
@@ -837,6 +846,127 @@ int tkv_amq_get_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment* 
                      uint64_t n_leaf_keys, const uint64_t* d_key_begin,
                      uint32_t flags, tkv_amq_get_result* d_result, uint32_t* d_query_visits,
                      tkv_amq_probe_metrics* d_metrics, tkv_amq_get_counts* d_counts, void* stream);
+
+/* Point lookup with values: tkv_amq_get_keys with the value rule of the reference's find_key
+ * (tree/algo/nodes.hpp:158-187) in place of "the first level that holds the key ends the lookup".
+ * The reference folds each level's answer into a running ValueView with combine_in_place
+ * (core/value_view.hpp:316-361) and stops when the folded value no longer needs_combine()
+ * (:279-285): a found OP_ADD_I32 is a delta and the lookup goes on through the older levels and the
+ * child, summing, until it meets an OP_WRITE or an OP_DELETE or runs out of tree.
+ * Arguments: everything tkv_amq_get_keys takes, with the same meaning, clamps and checks, and the
+ * leaves' values, parallel to leaf_keys (the value of item i belongs to leaf key i):
+ *  leaf_values          (device) the value bytes, leaf_values_bytes of them
+ *  leaf_value_offsets   (device, n_leaf_keys + 1 entries) item i owns [offsets[i], offsets[i+1]), both
+ *                       ends clamped to leaf_values_bytes, an end below its begin read as empty; or
+ *  leaf_value_stride    (offsets NULL) item i owns [i * stride, (i+1) * stride), clamped likewise
+ * No input causes a read outside [leaf_values, leaf_values + leaf_values_bytes).
+ * A value is the packed form the reference stores (unpack_value_view, core/packed_key_value.hpp:
+ * 18-23): byte 0 is the op (TKV_AMQ_OP_*, core/value_view.hpp:27-33), the data follows.  A value of
+ * length 0 reads as NOOP with no data.  The integer of a value is as_i32() (:248-262) by data
+ * length: 0 bytes: 0; 1, 2 or 3 bytes: the sign-extended little-endian integer; 4 or more: the
+ * first four bytes, little-endian.
+ * Per query the descent and the VISIT are exactly tkv_amq_get_keys' (pivot, levels, the filter asked
+ * as the path probe asks it, the leaf searched, ABSENT, UNSEARCHABLE, FLUSHED with its "leave the
+ * level") up to the point where it says FOUND.  There the item is TAKEN instead: its value is read
+ * and folded into the lookup's value.
+ *  - no value yet: the value becomes the item; key_index, leaf and where are the item's and stay
+ *    so; an ADD_I32 starts the accumulator at its integer
+ *  - the value is a pending ADD and the item's op is
+ *      WRITE     the value becomes WRITE of (accumulator + the item's integer)
+ *      DELETE    the value becomes WRITE of the accumulator
+ *      ADD_I32   the accumulator adds the item's integer and stays pending
+ *    (sums wrap modulo 2^32).  After the first of these folds the result carries
+ *    TKV_AMQ_VALUE_COMBINED: its value is the 4-byte integer i32, not an item's bytes.
+ *      any other op   the reference's "Bad combination of opcodes" (:331-333): the value is
+ *                unchanged, the result carries TKV_AMQ_VALUE_BAD_COMBINE, bad_combine_count + 1
+ * After the fold a value whose op is not ADD_I32 ends the lookup; a pending ADD leaves the level (the
+ * segment search answers kBreak on a found key, tree/algo/segments.hpp:202-205, and keys are unique
+ * in a level) and the lookup goes on with the next level or the child.  The reference nests -- each
+ * node's find_key starts from an empty value and hands its result up to be combined
+ * (nodes.hpp:176-180) -- which for the three combining ops equals this flat fold; for a bad
+ * combination it does not: one on the FIRST item taken at its depth (the child leaf is a depth of
+ * its own) is that node's whole result, which the parent's combine rejects, so it ends the lookup
+ * with the value unchanged; one after another item taken at the same depth goes on as after an ADD.
+ * A lookup that runs out of tree with the ADD pending reports op ADD_I32 and the accumulator, as
+ * the reference returns it to KVStore::get (kv_store.cpp:709-719).
+ *  d_result[n_queries]   (device, 16-byte aligned) one 32-byte record per query
+ *  d_query_visits, d_metrics, d_counts   as tkv_amq_get_keys'; d_counts is a tkv_amq_value_counts
+ * On any input in which no taken item is an ADD_I32, key_index, leaf, where, d_query_visits, all of
+ * d_metrics and the six shared counts equal tkv_amq_get_keys' exactly.
+ * One kernel launch, no workspace, no allocation, no synchronisation; capturable; the output is a
+ * function of the input.
+ * InvalidArgument, judged before a device is looked for: everything tkv_amq_get_keys refuses; a null
+ * leaf_values with n_leaf_keys > 0 and leaf_values_bytes > 0; the fixed form (no offsets) with
+ * stride 0 while n_leaf_keys > 0; d_result not 16-byte aligned.  A valid call on a machine without
+ * a device returns Unavailable. */
+#define TKV_AMQ_OP_DELETE 0u
+#define TKV_AMQ_OP_NOOP 1u
+#define TKV_AMQ_OP_WRITE 2u
+#define TKV_AMQ_OP_ADD_I32 3u
+#define TKV_AMQ_OP_PAGE_SLICE 4u
+#define TKV_AMQ_OP_NONE 0xffu /* `op` of a lookup that took no item */
+
+#define TKV_AMQ_VALUE_COMBINED 0x1u    /* the value is the record's i32, folded from several items */
+#define TKV_AMQ_VALUE_BAD_COMBINE 0x2u /* an item that cannot be combined with a pending ADD was met */
+
+typedef struct tkv_amq_value_result { /* 32 bytes */
+  uint64_t key_index;  /* the newest item taken (global index into leaf_keys); ~0ull if none */
+  uint64_t last_index; /* the last (oldest) item taken; == key_index when one was taken; ~0ull if none */
+  uint32_t leaf;       /* the key_index item's segment and ... */
+  uint32_t where;      /* ... depth << 8 | level, as in tkv_amq_get_result; 0xffffffff if none */
+  int32_t i32;         /* the accumulator if the newest item was an ADD_I32, else 0 */
+  uint8_t op;          /* the resolved op (TKV_AMQ_OP_*); TKV_AMQ_OP_NONE if no item was taken */
+  uint8_t flags;       /* TKV_AMQ_VALUE_* */
+  uint16_t n_items;    /* items taken, saturating */
+} tkv_amq_value_result;
+
+typedef struct tkv_amq_value_counts { /* 64 bytes, u64 each, ADDED to with atomics (zero to reset) */
+  uint64_t visit_count;        /* the first six as tkv_amq_get_counts, ... */
+  uint64_t leaf_search_count;
+  uint64_t found_count;        /* ... found_count: queries that ended with a value */
+  uint64_t absent_count;
+  uint64_t unsearchable_count;
+  uint64_t flushed_count;
+  uint64_t item_count;         /* items taken */
+  uint64_t bad_combine_count;  /* items met that could not be combined with a pending ADD */
+} tkv_amq_value_counts;
+
+int tkv_amq_get_values(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs, uint32_t n_segs,
+                       const tkv_amq_tree_node* nodes, uint64_t n_nodes,
+                       const tkv_amq_tree_segment* segments, uint64_t n_segments,
+                       const tkv_amq_tree_child* children, uint64_t n_children,
+                       const uint32_t* d_flushed_bounds, uint64_t n_flushed_bounds,
+                       const uint8_t* pivot_keys, const uint64_t* pivot_key_offsets,
+                       uint32_t pivot_key_stride, uint64_t n_pivot_keys,
+                       const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
+                       uint64_t n_queries,
+                       const uint8_t* leaf_keys, const uint64_t* leaf_key_offsets, uint32_t leaf_key_stride,
+                       uint64_t n_leaf_keys, const uint64_t* d_key_begin,
+                       const uint8_t* leaf_values, const uint64_t* leaf_value_offsets,
+                       uint32_t leaf_value_stride, uint64_t leaf_values_bytes,
+                       uint32_t flags, tkv_amq_value_result* d_result, uint32_t* d_query_visits,
+                       tkv_amq_probe_metrics* d_metrics, tkv_amq_value_counts* d_counts, void* stream);
+
+/* The value bytes of a batch of tkv_amq_get_values results, one fixed slot per query: d_out +
+ * i * out_stride receives the first min(len, out_stride) bytes of query i's value and nothing else
+ * in the slot is written; d_value_len[i] receives len, the full data length, so a truncation shows:
+ *  - a record whose key_index is at or past n_leaf_keys (so "none", ~0): 0 -- the records are caller
+ *    memory and are trusted no further
+ *  - TKV_AMQ_VALUE_COMBINED: 4, the record's i32 little-endian
+ *  - op DELETE, or an empty value: 0
+ *  - otherwise the data bytes of item key_index (the op byte excluded), from the value arrays as
+ *    tkv_amq_get_values takes and clamps them
+ * Sixteen lanes copy one value, eight bytes per lane and step: values start at
+ * any byte address.  Asynchronous on `stream`, one kernel launch, no allocation; capturable behind
+ * tkv_amq_get_values.  n_queries == 0 is OK.
+ * InvalidArgument, judged before a device is looked for: n_queries above 0xffffffff; a null d_result
+ * or d_value_len with n_queries > 0, or a null d_out with n_queries > 0 and out_stride > 0; d_result
+ * not 16-byte aligned; d_value_len not 4-byte aligned; a null leaf_values with n_leaf_keys > 0 and
+ * leaf_values_bytes > 0; the fixed form with stride 0 while n_leaf_keys > 0. */
+int tkv_amq_gather_values(const tkv_amq_value_result* d_result, uint64_t n_queries,
+                          const uint8_t* leaf_values, const uint64_t* leaf_value_offsets,
+                          uint32_t leaf_value_stride, uint64_t leaf_values_bytes, uint64_t n_leaf_keys,
+                          uint8_t* d_out, uint32_t out_stride, uint32_t* d_value_len, void* stream);
 
 /* Open built filters without a plan (a store restarting on a checkpoint, filter pages received
  * from elsewhere): reconstructs and validates one segment per filter from the filter bytes on

@@ -20,8 +20,10 @@
 //                                                                          open_filter_pages, scan_filters
 //   find_pivot_containing / find_key      tree/algo/nodes.hpp:48-71,158-187, tree/algo/segmented_levels.hpp:340-369
 //                                                                          TreeIndex, KeyQuery::walk_paths
-//   NodeAlgorithms::find_key, whole       tree/algo/nodes.hpp:158-187, tree/algo/segments.hpp:166-206
+//   NodeAlgorithms::find_key, no combine  tree/algo/nodes.hpp:158-187, tree/algo/segments.hpp:166-206
 //                                                                          TreeIndex::get_host, KeyQuery::get_keys
+//   ... with combine_in_place             core/value_view.hpp:316-361, core/packed_key_value.hpp:18-23
+//                                                                          TreeIndex::get_values_host, KeyQuery::get_values
 //
 // The single-leaf functions take the leaf's keys as host string views (the reference's
 // `items` range of EditView keys, tombstones included) and fill a host page payload
@@ -1330,6 +1332,104 @@ class TreeIndex
     get_host(keys, leaf_keys, key_begin, out, [](u32, std::string_view) { return true; });
   }
 
+  // as_i32() of a packed value's data (include/tkv_amq.h): 0 bytes: 0; 1..3: the sign-extended
+  // little-endian integer; 4 and more: the first four bytes.
+  static u32 value_i32(std::string_view data)
+  {
+    const usize m = std::min<usize>(data.size(), 4);
+    u32 x = 0;
+    for (usize j = 0; j < m; ++j) x |= (u32)(u8)data[j] << (8 * j);
+    if (m == 0 || m == 4) return x;
+    const u32 sign = u32{1} << (8 * m - 1);
+    return (x ^ sign) - sign;  // (modulo 2^32: the sign extension)
+  }
+
+  // The point lookup with values on the host (what tkv_amq_get_values computes, include/tkv_amq.h):
+  // get_host's visits, with every found item taken instead -- leaf_values[i] is the packed value
+  // of leaf key i (an op byte, then the data; an empty value reads as NOOP) -- and folded into the
+  // lookup's value: the first item is the value; a pending ADD_I32 takes a WRITE (the sum, as a
+  // WRITE), a DELETE (a WRITE of the accumulator) or another ADD_I32 (summed, still pending; sums
+  // wrap modulo 2^32); anything else is a bad combination, which leaves the value unchanged and ends
+  // the lookup if the item is the first taken at its depth (the child leaf is a depth of its own).
+  // A value that is no pending ADD ends the lookup; a pending ADD leaves the level.  maybe, visits:
+  // as get_host's.  counts (optional): item_count, found_count and bad_combine_count are set.
+  template <class Maybe>
+  void get_values_host(const std::vector<std::string_view>& keys, const std::vector<std::string_view>& leaf_keys,
+                       const std::vector<std::string_view>& leaf_values, const std::vector<u64>& key_begin,
+                       std::vector<tkv_amq_value_result>& out, Maybe&& maybe, std::vector<u32>* visits = nullptr,
+                       tkv_amq_value_counts* counts = nullptr) const
+  {
+    const tkv_amq_value_result none{~u64{0}, ~u64{0}, ~u32{0}, ~u32{0}, 0, (u8)TKV_AMQ_OP_NONE, 0, 0};
+    out.assign(keys.size(), none);
+    if (visits) visits->assign(keys.size(), 0);
+    if (counts) *counts = tkv_amq_value_counts{};
+    std::vector<std::string_view> pk(pivot_keys_.begin(), pivot_keys_.end());
+    const usize n_leaves = key_begin.empty() ? 0 : key_begin.size() - 1;
+    TreePaths o;
+    for (usize i = 0; i < keys.size(); ++i) {
+      o.clear(0);
+      walk_one(pk, keys[i], o);
+      tkv_amq_value_result r = none;
+      u32 left = ~u32{0}, n_visits = 0, acc = 0, n_items = 0, last_depth = ~u32{0};
+      for (usize e = 0; e < o.leaf.size(); ++e) {
+        if (o.where[e] == left) continue;
+        ++n_visits;
+        const u32 leaf = o.leaf[e];
+        if (!maybe(leaf, keys[i]) || leaf >= n_leaves) continue;
+        const u64 b0 = std::min<u64>(key_begin[leaf], leaf_keys.size());
+        const u64 e0 = std::max<u64>(std::min<u64>(key_begin[leaf + 1], leaf_keys.size()), b0);
+        const u64 b = (u64)(std::lower_bound(leaf_keys.begin() + b0, leaf_keys.begin() + e0, keys[i]) - leaf_keys.begin());
+        if (b == e0 || leaf_keys[b] != keys[i]) continue;
+        left = o.where[e];  // flushed or taken: either way the level is left (or the lookup ends)
+        if (b - b0 < o.flushed[e]) continue;
+        const std::string_view value = b < leaf_values.size() ? leaf_values[b] : std::string_view{};
+        const u32 op = value.empty() ? TKV_AMQ_OP_NOOP : (u8)value[0];
+        const u32 x = value.empty() ? 0 : value_i32(value.substr(1));
+        const u32 depth = o.where[e] >> 8;
+        const bool first_here = (o.where[e] & 0xffu) == TKV_AMQ_WALK_LEAF_LEVEL || depth != last_depth;
+        last_depth = depth;
+        r.last_index = b;
+        ++n_items;
+        if (counts) ++counts->item_count;
+        bool stop = true;
+        if (n_items == 1) {
+          r.key_index = b;
+          r.leaf = leaf;
+          r.where = o.where[e];
+          r.op = (u8)op;
+          if (op == TKV_AMQ_OP_ADD_I32) {
+            acc = x;
+            stop = false;
+          }
+        } else if (op == TKV_AMQ_OP_WRITE || op == TKV_AMQ_OP_DELETE) {
+          acc += op == TKV_AMQ_OP_WRITE ? x : 0;
+          r.op = (u8)TKV_AMQ_OP_WRITE;
+          r.flags |= TKV_AMQ_VALUE_COMBINED;
+        } else if (op == TKV_AMQ_OP_ADD_I32) {
+          acc += x;
+          r.flags |= TKV_AMQ_VALUE_COMBINED;
+          stop = false;
+        } else {
+          r.flags |= TKV_AMQ_VALUE_BAD_COMBINE;
+          if (counts) ++counts->bad_combine_count;
+          stop = first_here;
+        }
+        if (stop) break;
+      }
+      r.i32 = (int32_t)acc;
+      r.n_items = (uint16_t)std::min<u32>(n_items, 0xffff);
+      if (counts && n_items) ++counts->found_count;
+      out[i] = r;
+      if (visits) (*visits)[i] = n_visits;
+    }
+  }
+  void get_values_host(const std::vector<std::string_view>& keys, const std::vector<std::string_view>& leaf_keys,
+                       const std::vector<std::string_view>& leaf_values, const std::vector<u64>& key_begin,
+                       std::vector<tkv_amq_value_result>& out) const
+  {
+    get_values_host(keys, leaf_keys, leaf_values, key_begin, out, [](u32, std::string_view) { return true; });
+  }
+
   // The flat arrays on the device, uploaded once (pivot keys fixed-stride if they share a length).
   Status upload()
   {
@@ -1378,6 +1478,25 @@ class TreeIndex
                             keys_fixed_ ? key_stride_ : 0, pivot_keys_.size(), d_queries, d_query_offsets,
                             query_stride, n_queries, d_leaf_keys, d_leaf_key_offsets, leaf_key_stride, n_leaf_keys,
                             d_key_begin, flags, d_result, d_query_visits, d_metrics, d_counts, stream);
+  }
+
+  // tkv_amq_get_values over the uploaded tree (upload() first); every pointer is a device pointer
+  int get_values_device(int kind, const u8* d_filters, const tkv_amq_segment* d_segs, u32 n_segs, const u8* d_queries,
+                        const u64* d_query_offsets, u32 query_stride, u64 n_queries, const u8* d_leaf_keys,
+                        const u64* d_leaf_key_offsets, u32 leaf_key_stride, u64 n_leaf_keys, const u64* d_key_begin,
+                        const u8* d_leaf_values, const u64* d_leaf_value_offsets, u32 leaf_value_stride,
+                        u64 leaf_values_bytes, u32 flags, tkv_amq_value_result* d_result, u32* d_query_visits,
+                        tkv_amq_probe_metrics* d_metrics, tkv_amq_value_counts* d_counts,
+                        hipStream_t stream = nullptr) const
+  {
+    return tkv_amq_get_values(kind, d_filters, d_segs, n_segs, d_nodes_.get<tkv_amq_tree_node>(), nodes_.size(),
+                              d_segments_.get<tkv_amq_tree_segment>(), segments_.size(),
+                              d_children_.get<tkv_amq_tree_child>(), children_.size(), d_bounds_.get<u32>(),
+                              flushed_bounds_.size(), d_keys_.get(), keys_fixed_ ? nullptr : d_key_offs_.get<u64>(),
+                              keys_fixed_ ? key_stride_ : 0, pivot_keys_.size(), d_queries, d_query_offsets,
+                              query_stride, n_queries, d_leaf_keys, d_leaf_key_offsets, leaf_key_stride, n_leaf_keys,
+                              d_key_begin, d_leaf_values, d_leaf_value_offsets, leaf_value_stride, leaf_values_bytes,
+                              flags, d_result, d_query_visits, d_metrics, d_counts, stream);
   }
 
  private:
@@ -1813,6 +1932,83 @@ class KeyQuery
         hipMemcpy(&gc, d_counts, sizeof(gc), hipMemcpyDeviceToHost) != hipSuccess)
       return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy found keys");
     if (counts) *counts = gc;
+    Metrics& m = metrics();
+    m.total_filter_query_count.add(pm.total_filter_query_count);
+    m.no_filter_page_count.add(pm.no_filter_page_count);
+    m.page_id_mismatch_count.add(pm.page_id_mismatch_count);
+    m.filter_reject_count.add(pm.filter_reject_count);
+    m.filter_positive_count.add(pm.filter_positive_count);
+    m.filter_false_positive_count.add(pm.filter_false_positive_count);
+    return OkStatus();
+  }
+
+  // The lookup from keys to resolved values in one call (tkv_amq_get_values): get_keys with the
+  // value rule of the reference's find_key -- every found item's packed value folded as
+  // combine_in_place folds it, ADD_I32 deltas summed through the older levels and the child until a
+  // WRITE or a DELETE resolves them -- what TreeIndex::get_values_host computes on the host.
+  //  d_leaf_values, ...        the leaves' packed values, parallel to the leaf keys: offsets
+  //                            (n_leaf_keys + 1) or a fixed stride, and the buffer's size
+  //  out                       (out) per key: the tkv_amq_value_result record
+  //  slots, lengths, out_stride (out, optional; out_stride > 0) tkv_amq_gather_values behind the
+  //                            lookup: slots[i * out_stride ..] holds the first min(length,
+  //                            out_stride) bytes of key i's value, lengths[i] its full length
+  // Adds every visit to metrics(), as get_keys does.
+  Status get_values(FilterKind kind, const u8* d_filters, const tkv_amq_segment* d_segs,
+                    const std::vector<tkv_amq_segment>& segs, TreeIndex& tree, const u8* d_leaf_keys,
+                    const u64* d_leaf_key_offsets, u32 leaf_key_stride, u64 n_leaf_keys, const u8* d_leaf_values,
+                    const u64* d_leaf_value_offsets, u32 leaf_value_stride, u64 leaf_values_bytes,
+                    bool check_page_ids, std::vector<tkv_amq_value_result>& out,
+                    tkv_amq_value_counts* counts = nullptr, std::vector<u8>* slots = nullptr,
+                    std::vector<u32>* lengths = nullptr, u32 out_stride = 0)
+  {
+    const u64 n = keys_.size();
+    out.assign(n, tkv_amq_value_result{~u64{0}, ~u64{0}, ~u32{0}, ~u32{0}, 0, (u8)TKV_AMQ_OP_NONE, 0, 0});
+    if (counts) *counts = tkv_amq_value_counts{};
+    const bool gather = slots && lengths && out_stride;
+    if (gather) {
+      slots->assign(n * out_stride, 0);
+      lengths->assign(n, 0);
+    }
+    if (tkv_amq_device_count() == 0) return Status::from(TKV_AMQ_UNAVAILABLE, "no HIP device");
+    if (n == 0) return OkStatus();
+    TKV_AMQ_REQUIRE_OK(tree.upload());
+    DeviceBuffer d_keys, d_offs, d_result, d_tallies, d_slots, d_lengths;
+    constexpr usize kMetricsBytes = sizeof(tkv_amq_probe_metrics);
+    if (!d_result.resize(sizeof(tkv_amq_value_result) * n) ||
+        !d_tallies.resize(kMetricsBytes + sizeof(tkv_amq_value_counts)) ||
+        (gather && (!d_slots.resize(n * out_stride) || !d_lengths.resize(4 * n))))
+      return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+    bool fixed = false;
+    u32 stride = 16;
+    TKV_AMQ_REQUIRE_OK(detail::stage_keys(keys_, d_keys, d_offs, fixed, stride));
+    if (hipMemset(d_tallies.get(), 0, kMetricsBytes + sizeof(tkv_amq_value_counts)) != hipSuccess ||
+        (gather && hipMemset(d_slots.get(), 0, n * out_stride) != hipSuccess))
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemset counters");
+    auto* d_metrics = d_tallies.get<tkv_amq_probe_metrics>();
+    auto* d_counts = reinterpret_cast<tkv_amq_value_counts*>(d_tallies.get() + kMetricsBytes);
+    int st = tree.get_values_device((int)kind, d_filters, d_segs, (u32)segs.size(), d_keys.get(),
+                                    fixed ? nullptr : d_offs.get<u64>(), fixed ? stride : 0, n, d_leaf_keys,
+                                    d_leaf_key_offsets, leaf_key_stride, n_leaf_keys, nullptr, d_leaf_values,
+                                    d_leaf_value_offsets, leaf_value_stride, leaf_values_bytes,
+                                    check_page_ids ? TKV_AMQ_GET_CHECK_PAGE_ID : 0u,
+                                    d_result.get<tkv_amq_value_result>(), nullptr, d_metrics, d_counts);
+    if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_get_values");
+    if (gather) {
+      st = tkv_amq_gather_values(d_result.get<tkv_amq_value_result>(), n, d_leaf_values, d_leaf_value_offsets,
+                                 leaf_value_stride, leaf_values_bytes, n_leaf_keys, d_slots.get(), out_stride,
+                                 d_lengths.get<u32>(), nullptr);
+      if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_gather_values");
+    }
+    tkv_amq_probe_metrics pm{};
+    tkv_amq_value_counts vc{};
+    // (blocking copies on the null stream: they wait for the lookup and the gather)
+    if (hipMemcpy(out.data(), d_result.get(), sizeof(tkv_amq_value_result) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&pm, d_metrics, sizeof(pm), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&vc, d_counts, sizeof(vc), hipMemcpyDeviceToHost) != hipSuccess ||
+        (gather && (hipMemcpy(slots->data(), d_slots.get(), n * out_stride, hipMemcpyDeviceToHost) != hipSuccess ||
+                    hipMemcpy(lengths->data(), d_lengths.get(), 4 * n, hipMemcpyDeviceToHost) != hipSuccess)))
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy values");
+    if (counts) *counts = vc;
     Metrics& m = metrics();
     m.total_filter_query_count.add(pm.total_filter_query_count);
     m.no_filter_page_count.add(pm.no_filter_page_count);

@@ -18,7 +18,8 @@ from .filters import (BoolStatus, FilterPage, FilterPlan, KeyBatch, KeyQuery, Pa
                       verify_members_device, verify_members_workspace_bytes, find_keys,
                       find_keys_device, FindResult, FindCounts, TreeIndex, WalkResult, walk_paths,
                       walk_paths_device, walk_paths_workspace_bytes, get_keys, get_keys_device,
-                      GetResult, GetCounts)
+                      GetResult, GetCounts, get_values, get_values_device, gather_values_device,
+                      ValueResult, ValueCounts)
 
 __all__ = [
     "abi", "BLOOM", "VQF", "TkvAmqError", "BoolStatus", "FilterPage", "FilterPlan", "KeyBatch",
@@ -35,4 +36,5 @@ __all__ = [
     "verify_members_workspace_bytes", "find_keys", "find_keys_device", "FindResult", "FindCounts",
     "TreeIndex", "WalkResult", "walk_paths", "walk_paths_device", "walk_paths_workspace_bytes",
     "get_keys", "get_keys_device", "GetResult", "GetCounts",
+    "get_values", "get_values_device", "gather_values_device", "ValueResult", "ValueCounts",
 ]

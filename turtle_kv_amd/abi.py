@@ -100,6 +100,7 @@ EXPORTS = [
     "tkv_amq_find_keys",
     "tkv_amq_walk_paths_ws_bytes", "tkv_amq_walk_paths",
     "tkv_amq_get_keys",
+    "tkv_amq_get_values", "tkv_amq_gather_values",
 ]
 
 # tkv_amq_build_route: TKV_AMQ_ROUTE_* (a Bloom batch's route, or a VQF batch's decide stage),
@@ -160,6 +161,18 @@ GET_COUNTS_DTYPE = np.dtype([(n, "<u8") for n in GET_COUNTS_FIELDS])
 assert GET_COUNTS_DTYPE.itemsize == 48
 GET_CHECK_PAGE_ID = 0x1
 NO_WHERE = 0xFFFFFFFF      # `where` of a query that found nothing
+
+# tkv_amq_value_result (32 bytes), tkv_amq_value_counts (64 bytes), the ops of a packed value
+# (TKV_AMQ_OP_*) and the result flags (TKV_AMQ_VALUE_*)
+VALUE_RESULT_DTYPE = np.dtype([("key_index", "<u8"), ("last_index", "<u8"), ("leaf", "<u4"), ("where", "<u4"),
+                               ("i32", "<i4"), ("op", "u1"), ("flags", "u1"), ("n_items", "<u2")])
+assert VALUE_RESULT_DTYPE.itemsize == 32
+VALUE_COUNTS_FIELDS = GET_COUNTS_FIELDS + ("item_count", "bad_combine_count")
+VALUE_COUNTS_DTYPE = np.dtype([(n, "<u8") for n in VALUE_COUNTS_FIELDS])
+assert VALUE_COUNTS_DTYPE.itemsize == 64
+OP_DELETE, OP_NOOP, OP_WRITE, OP_ADD_I32, OP_PAGE_SLICE = range(5)
+OP_NONE = 0xFF             # `op` of a lookup that took no item
+VALUE_COMBINED, VALUE_BAD_COMBINE = 0x1, 0x2
 
 
 # tkv_amq_walk_paths: the flat tree (tkv_amq_tree_node / _segment / _child) and its limits
@@ -338,6 +351,17 @@ def lib(build_if_missing: bool = True):
                                        vp, vp, u32, u64,
                                        vp, vp, u32, u64, vp,
                                        u32, vp, vp, vp, vp, vp]
+    if hasattr(L, "tkv_amq_get_values"):
+        L.tkv_amq_get_values.restype = i32
+        L.tkv_amq_get_values.argtypes = [i32, vp, vp, u32,
+                                         vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, u32, u64,
+                                         vp, vp, u32, u64,
+                                         vp, vp, u32, u64, vp,
+                                         vp, vp, u32, u64,
+                                         u32, vp, vp, vp, vp, vp]
+    if hasattr(L, "tkv_amq_gather_values"):
+        L.tkv_amq_gather_values.restype = i32
+        L.tkv_amq_gather_values.argtypes = [vp, u64, vp, vp, u32, u64, u64, vp, u32, vp, vp]
     if hasattr(L, "tkv_amq_bloom_route"):
         L.tkv_amq_bloom_route_ws_bytes.restype = u64
         L.tkv_amq_bloom_route_ws_bytes.argtypes = [u64, u32]

@@ -5306,14 +5306,25 @@ __device__ inline void flush_get_tally(const GetTally& t, tkv_amq_probe_metrics*
   }
 }
 
+// What a lookup does with a found item is its Rule.  tkv_amq_get_keys': the first item found is
+// the result and ends the lookup; nothing is folded.  (GetValuesRule, below, folds: its take() folds
+// the item into the rule's state and says whether it is the lookup's first, step() is what the
+// descent does after it, write() stores the query's result.)
+struct GetKeysRule {
+  using Args = GetArgs;
+  using Tally = GetTally;
+  static constexpr bool kFolds = false;
+};
+
 // The descent of query i with test(leaf, page id) -> result bit | class << 1 as its filter test.
-template <int ORDER, typename Test>
-__device__ inline void get_one(const GetArgs& a, uint64_t i, GetTally& t, Test&& test)
+template <int ORDER, typename Rule = GetKeysRule, typename Test>
+__device__ inline void get_one(const typename Rule::Args& a, uint64_t i, typename Rule::Tally& t, Test&& test)
 {
   const OrderedQuery<ORDER> q(KeyArray{a.q, a.qoffs, a.qstride}, i);
   const KeyArray ks{a.keys, a.koffs, a.kstride};
   uint64_t r_key = ~0ull;
   uint32_t r_leaf = ~0u, r_where = ~0u, n_visits = 0;
+  [[maybe_unused]] Rule rule;
   // (always inlined, at both of its sites: as a function it would hold the lookup's state on the
   // stack.  The child leaf's site is where the lanes of a level tree meet again, so the second
   // copy costs code and no divergence.)
@@ -5335,16 +5346,27 @@ __device__ inline void get_one(const GetArgs& a, uint64_t i, GetTally& t, Test&&
         if (b < e && q.equal(ks, b)) {
           // below the bound the item "has been flushed from this segment": the level is left
           outcome = b - b0 < flushed_bound ? kGetFlushed : kGetFound;
-          if (outcome == kGetFound) {
-            r_key = b;
-            r_leaf = leaf;
-            r_where = where;
+          if constexpr (Rule::kFolds) {
+            if (outcome == kGetFound && rule.take(a, t, b, where)) {
+              r_key = b;
+              r_leaf = leaf;
+              r_where = where;
+            }
+          } else {
+            if (outcome == kGetFound) {
+              r_key = b;
+              r_leaf = leaf;
+              r_where = where;
+            }
           }
         }
       }
     }
     t.add(r, outcome);
-    return outcome == kGetFound ? kWalkStop : outcome == kGetFlushed ? kWalkLeaveLevel : kWalkContinue;
+    if constexpr (Rule::kFolds)
+      return outcome == kGetFound ? rule.step() : outcome == kGetFlushed ? kWalkLeaveLevel : kWalkContinue;
+    else
+      return outcome == kGetFound ? kWalkStop : outcome == kGetFlushed ? kWalkLeaveLevel : kWalkContinue;
   };
   walk_tree(
       a, [&](uint32_t, uint32_t key_begin, uint32_t pivot_count) { return find_pivot<ORDER>(a, q, key_begin, pivot_count); },
@@ -5356,25 +5378,28 @@ __device__ inline void get_one(const GetArgs& a, uint64_t i, GetTally& t, Test&&
       },
       [&](uint32_t index, uint64_t page_id, uint32_t where) { visit(index, page_id, 0u, where); });
   t.total += n_visits;
-  *reinterpret_cast<ulonglong2*>(a.result + i) = ulonglong2{r_key, mk64(r_leaf, r_where)};
+  if constexpr (Rule::kFolds)
+    rule.write(a, i, t, r_key, r_leaf, r_where);
+  else
+    *reinterpret_cast<ulonglong2*>(a.result + i) = ulonglong2{r_key, mk64(r_leaf, r_where)};
   if (a.visits) a.visits[i] = n_visits;
 }
 
 // ORDER: the key order's mode over the three key sides (tkv_amq_key_order.h); HASH: the hash's
 // mode of the query side, as the path probe chooses it.
-template <int KIND, int ORDER, int HASH>
-__device__ inline void get_keys_tiles(const GetArgs& a)
+template <int KIND, int ORDER, int HASH, typename Rule = GetKeysRule>
+__device__ inline void get_keys_tiles(const typename Rule::Args& a)
 {
   // Bloom: the lane's block slot (16-byte keys) or its cache of bit indices (32 bytes and more)
   __shared__ uint4 s_blk[KIND == TKV_AMQ_BLOOM ? kGetThreads * kProbeSlotWords / 4 : 1];
   uint4* slot = s_blk + (KIND == TKV_AMQ_BLOOM ? threadIdx.x * (kProbeSlotWords / 4) : 0u);
-  GetTally t;
+  typename Rule::Tally t;
   for (uint32_t w = blockIdx.x; w < a.n_tiles; w += gridDim.x) {
     const uint64_t i = (uint64_t)w * kGetThreads + threadIdx.x;
     if (i >= a.n_queries) continue;
     if constexpr (KIND == TKV_AMQ_VQF) {
       const uint64_t h = vqf_query_hash<HASH>(a.q, a.qoffs, a.qstride, i);
-      get_one<ORDER>(a, i, t, [&](uint32_t leaf, const PageIdIs& id) {
+      get_one<ORDER, Rule>(a, i, t, [&](uint32_t leaf, const PageIdIs& id) {
         return vqf_probe_one<true>(a.filters, a.segs_plan, a.n_plan, leaf, h, id);
       });
     } else if constexpr (HASH == kKey16) {
@@ -5383,20 +5408,23 @@ __device__ inline void get_keys_tiles(const GetArgs& a)
       const uint64_t h0 = x.h0();
       const BloomBits16 bits(x);
       bloom_entry16_park(x, slot);
-      get_one<ORDER>(a, i, t, [&](uint32_t leaf, const PageIdIs& id) {
+      get_one<ORDER, Rule>(a, i, t, [&](uint32_t leaf, const PageIdIs& id) {
         return bloom_entry16_test(h0, bits, bloom_entry16_fetch<true>(a.filters, a.segs_plan, a.n_plan, leaf, h0, id, 0u), slot);
       });
     } else {
       with_bloom_key_at<HASH>(a.q, a.qoffs, a.qstride, i, [&](const auto& x) {
         const uint64_t h0 = x.h0();
         BloomBitSource<std::decay_t<decltype(x)>> bit_of{x, reinterpret_cast<uint16_t*>(slot)};
-        get_one<ORDER>(a, i, t, [&](uint32_t leaf, const PageIdIs& id) {
+        get_one<ORDER, Rule>(a, i, t, [&](uint32_t leaf, const PageIdIs& id) {
           return bloom_entry_test<true>(a.filters, a.segs_plan, a.n_plan, leaf, h0, id, 0u, bit_of);
         });
       });
     }
   }
-  flush_get_tally(t, a.metrics, a.counts);
+  if constexpr (Rule::kFolds)
+    flush_value_tally(t, a.metrics, a.vcounts);
+  else
+    flush_get_tally(t, a.metrics, a.counts);
 }
 
 // Occupancy: every step of a lookup is a dependent read, so the throughput comes from waves in
@@ -5407,6 +5435,203 @@ template <int KIND, int ORDER, int HASH>
 __global__ __launch_bounds__(kGetThreads) void get_keys_kernel(GetArgs a)
 {
   get_keys_tiles<KIND, ORDER, HASH>(a);
+}
+
+// ---------------------------------------------------------------------------------------
+// Point lookup with values (tkv_amq_get_values): the same descent with find_key's value rule
+// ---------------------------------------------------------------------------------------
+// The visit is get_keys' (get_one, with GetValuesRule as its Rule); what differs is what FOUND does: the item's packed value
+// (op byte, data) is folded into the lane's value as combine_in_place folds it
+// (core/value_view.hpp:316-361) and the descent goes on while an ADD_I32 is pending.
+struct ValueArray {
+  const uint8_t* values;
+  const uint64_t* offs;  // n_keys + 1 entries, or null: the fixed form
+  uint32_t stride;
+  uint64_t bytes;
+};
+
+struct ValueArgs : GetArgs {
+  ValueArray v;
+  tkv_amq_value_result* vresult;
+  tkv_amq_value_counts* vcounts;
+};
+
+// Item i's bytes [b, e), both ends clamped to the buffer, e >= b.
+__device__ inline void value_range(const ValueArray& v, uint64_t i, uint64_t& b, uint64_t& e)
+{
+  if (v.offs) {
+    b = min(v.offs[i], v.bytes);
+    e = max(min(v.offs[i + 1], v.bytes), b);
+  } else {
+    // (a product past 2^64 lies past any buffer)
+    b = __umul64hi(i, v.stride) ? v.bytes : min(i * v.stride, v.bytes);
+    e = v.bytes - b < v.stride ? v.bytes : b + v.stride;
+  }
+}
+
+// as_i32() of n data bytes at p (core/value_view.hpp:248-262): 0 bytes: 0; 1..3: the sign-extended
+// little-endian integer; 4 and more: the first four.  Byte loads: values start at any address and
+// an item is read once per hit.
+__device__ inline uint32_t value_i32(const uint8_t* p, uint64_t n)
+{
+  const uint32_t m = n < 4 ? (uint32_t)n : 4u;
+  uint32_t x = 0;
+  for (uint32_t j = 0; j < m; ++j) x |= (uint32_t)p[j] << (8 * j);
+  const uint32_t sh = 32 - 8 * m;
+  return m == 0 ? 0u : (uint32_t)((int32_t)(x << sh) >> sh);
+}
+
+struct ValueTally : GetTally {
+  uint32_t valued = 0, bad = 0;  // (GetTally::found counts the items taken)
+};
+
+__device__ inline void flush_value_tally(const ValueTally& t, tkv_amq_probe_metrics* m, tkv_amq_value_counts* c)
+{
+  const uint32_t total = wave_sum(t.total), no_filter = wave_sum(t.no_filter), mismatch = wave_sum(t.mismatch),
+                 positive = wave_sum(t.positive), false_pos = wave_sum(t.false_pos), items = wave_sum(t.found),
+                 unsearchable = wave_sum(t.unsearchable), flushed = wave_sum(t.flushed),
+                 valued = wave_sum(t.valued), bad = wave_sum(t.bad);
+  if (__lane_id() != 0) return;
+  const uint32_t maybe = no_filter + mismatch + positive;
+  const uint32_t absent = maybe - unsearchable - items - flushed;
+  // one atomic per non-zero counter per wave
+  if (m) {
+    const uint32_t v[6] = {total, no_filter, mismatch, total - maybe, positive, false_pos};
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(m);
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+      if (v[j]) atomicAdd(&d[j], (unsigned long long)v[j]);
+  }
+  if (c) {
+    const uint32_t v[8] = {total, maybe - unsearchable, valued, absent, unsearchable, flushed, items, bad};
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(c);
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (v[j]) atomicAdd(&d[j], (unsigned long long)v[j]);
+  }
+}
+
+// tkv_amq_get_values' rule: the lane's value -- its op, the accumulator of a pending or resolved ADD,
+// flags, the items taken, the last one's index and depth (a bad combination on a node's first item is
+// the node's whole answer) -- and the step the last fold chose.
+struct GetValuesRule {
+  using Args = ValueArgs;
+  using Tally = ValueTally;
+  static constexpr bool kFolds = true;
+  uint64_t r_last = ~0ull;
+  uint32_t op = TKV_AMQ_OP_NONE, acc = 0, flags = 0, n_items = 0, last_depth = ~0u;
+  WalkStep next = kWalkStop;
+  // folds item b, found at `where`; true if it is the lookup's first (the result's key_index)
+  __device__ inline bool take(const Args& a, Tally& t, uint64_t b, uint32_t where)
+  {
+    uint64_t vb, ve;
+    value_range(a.v, b, vb, ve);
+    const uint32_t item_op = ve > vb ? a.v.values[vb] : TKV_AMQ_OP_NOOP;  // (an empty value is a NOOP)
+    const uint32_t item_i32 = ve > vb ? value_i32(a.v.values + vb + 1, ve - vb - 1) : 0u;
+    const uint32_t depth = where >> 8;
+    // (the child leaf is a depth of its own)
+    const bool first_here = (where & 0xffu) == TKV_AMQ_WALK_LEAF_LEVEL || depth != last_depth;
+    last_depth = depth;
+    r_last = b;
+    ++n_items;
+    next = kWalkStop;
+    if (n_items == 1) {
+      op = item_op;
+      if (item_op == TKV_AMQ_OP_ADD_I32) {
+        acc = item_i32;
+        next = kWalkLeaveLevel;
+      }
+    } else if (item_op == TKV_AMQ_OP_WRITE || item_op == TKV_AMQ_OP_DELETE) {
+      // (the lookup is here only with an ADD pending)
+      acc += item_op == TKV_AMQ_OP_WRITE ? item_i32 : 0u;
+      op = TKV_AMQ_OP_WRITE;
+      flags |= TKV_AMQ_VALUE_COMBINED;
+    } else if (item_op == TKV_AMQ_OP_ADD_I32) {
+      acc += item_i32;
+      flags |= TKV_AMQ_VALUE_COMBINED;
+      next = kWalkLeaveLevel;
+    } else {
+      flags |= TKV_AMQ_VALUE_BAD_COMBINE;
+      ++t.bad;
+      next = first_here ? kWalkStop : kWalkLeaveLevel;
+    }
+    return n_items == 1;
+  }
+  __device__ inline WalkStep step() const { return next; }
+  __device__ inline void write(const Args& a, uint64_t i, Tally& t, uint64_t r_key, uint32_t r_leaf,
+                               uint32_t r_where) const
+  {
+    t.valued += n_items != 0;
+    uint4* out = reinterpret_cast<uint4*>(a.vresult + i);
+    out[0] = uint4{(uint32_t)r_key, (uint32_t)(r_key >> 32), (uint32_t)r_last, (uint32_t)(r_last >> 32)};
+    out[1] = uint4{r_leaf, r_where, acc, op | (flags << 8) | (min(n_items, 0xffffu) << 16)};
+  }
+};
+
+// Occupancy: as get_keys_kernel, plus the value's state: no form asks for more waves, none uses
+// scratch (DESIGN.md section 17 has the table).
+template <int KIND, int ORDER, int HASH>
+__global__ __launch_bounds__(kGetThreads) void get_values_kernel(ValueArgs a)
+{
+  get_keys_tiles<KIND, ORDER, HASH, GetValuesRule>(a);
+}
+
+// tkv_amq_gather_values: sixteen lanes per value, eight bytes per lane and step.  A value of the
+// reference's default shape (about 100 data bytes behind an op byte, at any byte address) is one
+// step: the sixteen lanes read one or two consecutive 128-byte lines and a wave writes four
+// consecutive slots.  One lane per value would walk 64 distant lines per instruction; one wave per
+// value would leave a third of its lanes idle at a byte each.
+constexpr uint32_t kGatherLanes = 16, kGatherThreads = 256, kGatherPerBlock = kGatherThreads / kGatherLanes;
+
+struct GatherArgs {
+  const tkv_amq_value_result* result;
+  uint64_t n_queries, n_keys;
+  ValueArray v;
+  uint8_t* out;
+  uint32_t out_stride;
+  uint32_t* len;
+};
+
+__global__ __launch_bounds__(kGatherThreads) void gather_values_kernel(GatherArgs a)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * kGatherPerBlock + threadIdx.x / kGatherLanes;
+  const uint32_t sub = threadIdx.x % kGatherLanes;
+  if (i >= a.n_queries) return;
+  const uint4* rp = reinterpret_cast<const uint4*>(a.result + i);
+  const uint4 r0 = rp[0], r1 = rp[1];  // {key_index, last_index}, {leaf, where, i32, op | flags | n_items}
+  const uint64_t key = mk64(r0.x, r0.y);
+  const uint32_t op = r1.w & 0xffu, flags = (r1.w >> 8) & 0xffu;
+  uint64_t len = 0;
+  const uint8_t* src = nullptr;  // null: the record's own i32
+  if (key < a.n_keys) {
+    if (flags & TKV_AMQ_VALUE_COMBINED) {
+      len = 4;
+    } else if (op != TKV_AMQ_OP_DELETE) {
+      uint64_t vb, ve;
+      value_range(a.v, key, vb, ve);
+      if (ve > vb) {
+        len = ve - vb - 1;
+        src = a.v.values + vb + 1;
+      }
+    }
+  }
+  if (sub == 0) a.len[i] = len > 0xffffffffull ? 0xffffffffu : (uint32_t)len;
+  const uint32_t n = len < a.out_stride ? (uint32_t)len : a.out_stride;
+  uint8_t* dst = a.out + i * a.out_stride;
+  if (!src) {
+    // (n <= 4: the integer, little-endian, by lane 0)
+    if (sub == 0)
+      for (uint32_t j = 0; j < n; ++j) dst[j] = (uint8_t)(r1.z >> (8 * j));
+    return;
+  }
+  for (uint32_t o = 8 * sub; o < n; o += 8 * kGatherLanes) {
+    if (o + 8 <= n && (reinterpret_cast<uintptr_t>(dst + o) & 7) == 0) {
+      *reinterpret_cast<uint64_t*>(dst + o) = ld64_unaligned(src + o);
+    } else {
+      const uint32_t m = n - o < 8 ? n - o : 8;
+      for (uint32_t j = 0; j < m; ++j) dst[o + j] = src[o + j];
+    }
+  }
 }
 
 __global__ __launch_bounds__(256) void gen_keys16_kernel(uint64_t seed, uint64_t first, uint64_t n,
@@ -7553,18 +7778,20 @@ int tkv_amq_path_probe(int kind, const uint8_t* d_filters, const tkv_amq_segment
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
 
-int tkv_amq_get_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs, uint32_t n_segs,
-                     const tkv_amq_tree_node* nodes, uint64_t n_nodes, const tkv_amq_tree_segment* segments,
-                     uint64_t n_segments, const tkv_amq_tree_child* children, uint64_t n_children,
-                     const uint32_t* d_flushed_bounds, uint64_t n_flushed_bounds, const uint8_t* pivot_keys,
-                     const uint64_t* pivot_key_offsets, uint32_t pivot_key_stride, uint64_t n_pivot_keys,
-                     const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
-                     uint64_t n_queries, const uint8_t* leaf_keys, const uint64_t* leaf_key_offsets,
-                     uint32_t leaf_key_stride, uint64_t n_leaf_keys, const uint64_t* d_key_begin, uint32_t flags,
-                     tkv_amq_get_result* d_result, uint32_t* d_query_visits, tkv_amq_probe_metrics* d_metrics,
-                     tkv_amq_get_counts* d_counts, void* stream)
+// The argument checks of tkv_amq_get_keys and tkv_amq_get_values, everything but the result pointer's
+// own (judged first, so a bad call is InvalidArgument with or without a device), and the launch's
+// arguments filled from them.  `order`: one order for the pivots and the leaves.
+static int get_prepare(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs, uint32_t n_segs,
+                       const tkv_amq_tree_node* nodes, uint64_t n_nodes, const tkv_amq_tree_segment* segments,
+                       uint64_t n_segments, const tkv_amq_tree_child* children, uint64_t n_children,
+                       const uint32_t* d_flushed_bounds, uint64_t n_flushed_bounds, const uint8_t* pivot_keys,
+                       const uint64_t* pivot_key_offsets, uint32_t pivot_key_stride, uint64_t n_pivot_keys,
+                       const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
+                       uint64_t n_queries, const uint8_t* leaf_keys, const uint64_t* leaf_key_offsets,
+                       uint32_t leaf_key_stride, uint64_t n_leaf_keys, const uint64_t* d_key_begin, uint32_t flags,
+                       const void* d_result, uint32_t* d_query_visits, tkv_amq_probe_metrics* d_metrics,
+                       const void* d_counts, GetArgs& a, int& order, int& hash_mode)
 {
-  // (the arguments are judged first, so a bad call is InvalidArgument with or without a device)
   constexpr uint64_t kMax = 0xffffffffull;
   if (kind != TKV_AMQ_BLOOM && kind != TKV_AMQ_VQF) return TKV_AMQ_INVALID_ARGUMENT;
   if (flags & ~TKV_AMQ_GET_CHECK_PAGE_ID) return TKV_AMQ_INVALID_ARGUMENT;
@@ -7585,11 +7812,8 @@ int tkv_amq_get_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment* 
       (reinterpret_cast<uintptr_t>(d_query_visits) & 3))
     return TKV_AMQ_INVALID_ARGUMENT;
   // the hash's mode is the path probe's, with its rule for 16-byte queries
-  const int hash_mode = key_mode(query_offsets, query_stride);
+  hash_mode = key_mode(query_offsets, query_stride);
   if (hash_mode == kKey16 && (reinterpret_cast<uintptr_t>(queries) & 15)) return TKV_AMQ_INVALID_ARGUMENT;
-  if (tkv_amq_device_count() == 0) return TKV_AMQ_UNAVAILABLE;
-  if (n_queries == 0) return TKV_AMQ_OK;
-  GetArgs a;
   a.nodes = nodes;
   a.segs = segments;
   a.children = children;
@@ -7616,31 +7840,135 @@ int tkv_amq_get_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment* 
   a.n_tiles = (uint32_t)div_up(n_queries, kGetThreads);
   a.n_keys = n_leaf_keys;
   a.key_begin = d_key_begin;
-  a.result = d_result;
+  a.result = nullptr;
   a.visits = d_query_visits;
   a.metrics = d_metrics;
-  a.counts = d_counts;
-  // one order for the pivots and the leaves: a fast mode only if all three sides have its shape
+  a.counts = nullptr;
+  // a fast mode only if all three sides have its shape
   const KeyArray qa{queries, query_offsets, query_stride};
   const int op = key_order_mode(qa, KeyArray{pivot_keys, pivot_key_offsets, pivot_key_stride});
   const int ol = key_order_mode(qa, KeyArray{leaf_keys, leaf_key_offsets, leaf_key_stride});
-  const int order = op == ol ? op : (int)kOrderAny;
-  const dim3 grid(a.n_tiles < kGetMaxGrid ? a.n_tiles : kGetMaxGrid), block(kGetThreads);
-  const hipStream_t s = as_stream(stream);
-  auto launch = [&](auto K) {
-    constexpr int KIND = decltype(K)::value;
+  order = op == ol ? op : (int)kOrderAny;
+  return TKV_AMQ_OK;
+}
+
+// launch(KIND, ORDER, HASH as integral constants) for the form the key shapes choose
+extern "C++" template <typename Launch>
+static void with_get_form(int kind, int order, int hash_mode, Launch&& launch)
+{
+  auto pick = [&](auto K) {
     if (order == kOrder16) {
-      hipLaunchKernelGGL((get_keys_kernel<KIND, kOrder16, kKey16>), grid, block, 0, s, a);
+      launch(K, KeyModeC<kOrder16>{}, KeyModeC<kKey16>{});
     } else if (order == kOrder24) {
-      hipLaunchKernelGGL((get_keys_kernel<KIND, kOrder24, kKeyFixed>), grid, block, 0, s, a);
+      launch(K, KeyModeC<kOrder24>{}, KeyModeC<kKeyFixed>{});
     } else {
-      with_key_mode(hash_mode, [&](auto M) {
-        hipLaunchKernelGGL((get_keys_kernel<KIND, kOrderAny, decltype(M)::value>), grid, block, 0, s, a);
-      });
+      with_key_mode(hash_mode, [&](auto M) { launch(K, KeyModeC<kOrderAny>{}, M); });
     }
   };
-  if (kind == TKV_AMQ_BLOOM) launch(KeyModeC<TKV_AMQ_BLOOM>{});
-  else launch(KeyModeC<TKV_AMQ_VQF>{});
+  if (kind == TKV_AMQ_BLOOM) pick(KeyModeC<TKV_AMQ_BLOOM>{});
+  else pick(KeyModeC<TKV_AMQ_VQF>{});
+}
+
+int tkv_amq_get_keys(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs, uint32_t n_segs,
+                     const tkv_amq_tree_node* nodes, uint64_t n_nodes, const tkv_amq_tree_segment* segments,
+                     uint64_t n_segments, const tkv_amq_tree_child* children, uint64_t n_children,
+                     const uint32_t* d_flushed_bounds, uint64_t n_flushed_bounds, const uint8_t* pivot_keys,
+                     const uint64_t* pivot_key_offsets, uint32_t pivot_key_stride, uint64_t n_pivot_keys,
+                     const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
+                     uint64_t n_queries, const uint8_t* leaf_keys, const uint64_t* leaf_key_offsets,
+                     uint32_t leaf_key_stride, uint64_t n_leaf_keys, const uint64_t* d_key_begin, uint32_t flags,
+                     tkv_amq_get_result* d_result, uint32_t* d_query_visits, tkv_amq_probe_metrics* d_metrics,
+                     tkv_amq_get_counts* d_counts, void* stream)
+{
+  GetArgs a;
+  int order, hash_mode;
+  const int st = get_prepare(kind, d_filters, d_segs, n_segs, nodes, n_nodes, segments, n_segments, children,
+                             n_children, d_flushed_bounds, n_flushed_bounds, pivot_keys, pivot_key_offsets,
+                             pivot_key_stride, n_pivot_keys, queries, query_offsets, query_stride, n_queries,
+                             leaf_keys, leaf_key_offsets, leaf_key_stride, n_leaf_keys, d_key_begin, flags, d_result,
+                             d_query_visits, d_metrics, d_counts, a, order, hash_mode);
+  if (st != TKV_AMQ_OK) return st;
+  if (tkv_amq_device_count() == 0) return TKV_AMQ_UNAVAILABLE;
+  if (n_queries == 0) return TKV_AMQ_OK;
+  a.result = d_result;
+  a.counts = d_counts;
+  const dim3 grid(a.n_tiles < kGetMaxGrid ? a.n_tiles : kGetMaxGrid), block(kGetThreads);
+  const hipStream_t s = as_stream(stream);
+  with_get_form(kind, order, hash_mode, [&](auto K, auto O, auto H) {
+    hipLaunchKernelGGL((get_keys_kernel<decltype(K)::value, decltype(O)::value, decltype(H)::value>), grid, block, 0,
+                       s, a);
+  });
+  return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
+}
+
+// the checks the two value entry points share
+static bool value_array_ok(const uint8_t* leaf_values, const uint64_t* leaf_value_offsets, uint32_t leaf_value_stride,
+                           uint64_t leaf_values_bytes, uint64_t n_leaf_keys)
+{
+  if (n_leaf_keys && leaf_values_bytes && !leaf_values) return false;
+  return !(n_leaf_keys && !leaf_value_offsets && !leaf_value_stride);
+}
+
+int tkv_amq_get_values(int kind, const uint8_t* d_filters, const tkv_amq_segment* d_segs, uint32_t n_segs,
+                       const tkv_amq_tree_node* nodes, uint64_t n_nodes, const tkv_amq_tree_segment* segments,
+                       uint64_t n_segments, const tkv_amq_tree_child* children, uint64_t n_children,
+                       const uint32_t* d_flushed_bounds, uint64_t n_flushed_bounds, const uint8_t* pivot_keys,
+                       const uint64_t* pivot_key_offsets, uint32_t pivot_key_stride, uint64_t n_pivot_keys,
+                       const uint8_t* queries, const uint64_t* query_offsets, uint32_t query_stride,
+                       uint64_t n_queries, const uint8_t* leaf_keys, const uint64_t* leaf_key_offsets,
+                       uint32_t leaf_key_stride, uint64_t n_leaf_keys, const uint64_t* d_key_begin,
+                       const uint8_t* leaf_values, const uint64_t* leaf_value_offsets, uint32_t leaf_value_stride,
+                       uint64_t leaf_values_bytes, uint32_t flags, tkv_amq_value_result* d_result,
+                       uint32_t* d_query_visits, tkv_amq_probe_metrics* d_metrics, tkv_amq_value_counts* d_counts,
+                       void* stream)
+{
+  ValueArgs a;
+  int order, hash_mode;
+  const int st = get_prepare(kind, d_filters, d_segs, n_segs, nodes, n_nodes, segments, n_segments, children,
+                             n_children, d_flushed_bounds, n_flushed_bounds, pivot_keys, pivot_key_offsets,
+                             pivot_key_stride, n_pivot_keys, queries, query_offsets, query_stride, n_queries,
+                             leaf_keys, leaf_key_offsets, leaf_key_stride, n_leaf_keys, d_key_begin, flags, d_result,
+                             d_query_visits, d_metrics, d_counts, a, order, hash_mode);
+  if (st != TKV_AMQ_OK) return st;
+  if (!value_array_ok(leaf_values, leaf_value_offsets, leaf_value_stride, leaf_values_bytes, n_leaf_keys))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  if (tkv_amq_device_count() == 0) return TKV_AMQ_UNAVAILABLE;
+  if (n_queries == 0) return TKV_AMQ_OK;
+  a.v = ValueArray{leaf_values, leaf_value_offsets, leaf_value_stride, leaf_values_bytes};
+  a.vresult = d_result;
+  a.vcounts = d_counts;
+  const dim3 grid(a.n_tiles < kGetMaxGrid ? a.n_tiles : kGetMaxGrid), block(kGetThreads);
+  const hipStream_t s = as_stream(stream);
+  with_get_form(kind, order, hash_mode, [&](auto K, auto O, auto H) {
+    hipLaunchKernelGGL((get_values_kernel<decltype(K)::value, decltype(O)::value, decltype(H)::value>), grid, block,
+                       0, s, a);
+  });
+  return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
+}
+
+int tkv_amq_gather_values(const tkv_amq_value_result* d_result, uint64_t n_queries, const uint8_t* leaf_values,
+                          const uint64_t* leaf_value_offsets, uint32_t leaf_value_stride, uint64_t leaf_values_bytes,
+                          uint64_t n_leaf_keys, uint8_t* d_out, uint32_t out_stride, uint32_t* d_value_len,
+                          void* stream)
+{
+  if (n_queries > 0xffffffffull) return TKV_AMQ_INVALID_ARGUMENT;
+  if (n_queries && (!d_result || !d_value_len || (out_stride && !d_out))) return TKV_AMQ_INVALID_ARGUMENT;
+  if ((reinterpret_cast<uintptr_t>(d_result) & 15) || (reinterpret_cast<uintptr_t>(d_value_len) & 3))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  if (!value_array_ok(leaf_values, leaf_value_offsets, leaf_value_stride, leaf_values_bytes, n_leaf_keys))
+    return TKV_AMQ_INVALID_ARGUMENT;
+  if (tkv_amq_device_count() == 0) return TKV_AMQ_UNAVAILABLE;
+  if (n_queries == 0) return TKV_AMQ_OK;
+  GatherArgs a;
+  a.result = d_result;
+  a.n_queries = n_queries;
+  a.n_keys = n_leaf_keys;
+  a.v = ValueArray{leaf_values, leaf_value_offsets, leaf_value_stride, leaf_values_bytes};
+  a.out = d_out;
+  a.out_stride = out_stride;
+  a.len = d_value_len;
+  hipLaunchKernelGGL(gather_values_kernel, dim3((uint32_t)div_up(n_queries, kGatherPerBlock)), dim3(kGatherThreads), 0,
+                     as_stream(stream), a);
   return hipGetLastError() == hipSuccess ? TKV_AMQ_OK : TKV_AMQ_INTERNAL;
 }
 

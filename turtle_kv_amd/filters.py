@@ -1378,6 +1378,130 @@ def get_keys(plan_or_opened, filters, tree: TreeIndex, queries: KeyBatch, leaf_k
 
 
 # ---------------------------------------------------------------------------------------
+# point lookup with values: the same descent, the found items folded as combine_in_place folds them
+# ---------------------------------------------------------------------------------------
+class ValueCounts:
+    """Device-side tkv_amq_value_counts that get_values launches add to; `collect()` reads them."""
+
+    def __init__(self, device=None):
+        torch = _torch()
+        self.counts = torch.zeros(len(abi.VALUE_COUNTS_FIELDS), dtype=torch.int64, device=device or "cuda")
+
+    def reset(self) -> None:
+        self.counts.zero_()
+
+    def collect(self) -> dict:
+        return dict(zip(abi.VALUE_COUNTS_FIELDS, (int(v) for v in self.counts.cpu().tolist())))
+
+
+@dataclass
+class ValueResult:
+    """What get_values leaves on the device: `raw`, the tkv_amq_value_result array (uint8 [32 *
+    n_queries], abi.VALUE_RESULT_DTYPE records), views of its key_index, leaf and where (as
+    GetResult's), `visits` if asked for and, with gather=out_stride, `slots` (uint8 [n_queries,
+    out_stride]; bytes past a value's length are not written) and `lengths` (int32 [n_queries], the
+    full data length of each value)."""
+    key_index: object                    # int64 [n_queries]
+    leaf: object                         # int32 [n_queries]
+    where: object                        # int32 [n_queries]
+    visits: object = None                # int32 [n_queries], or None
+    raw: object = field(default=None, repr=False)
+    slots: object = None
+    lengths: object = None
+
+    def records(self) -> np.ndarray:
+        """The records on the host (a copy; synchronises)."""
+        n = int(self.key_index.numel())
+        return self.raw[:32 * n].cpu().numpy().view(abi.VALUE_RESULT_DTYPE)
+
+
+def get_values_device(kind: int, filters, d_segs, n_segs: int, d_nodes, n_nodes: int, d_segments,
+                      n_segments: int, d_children, n_children: int, d_flushed_bounds, n_flushed_bounds: int,
+                      pivot_keys, pivot_key_offsets, pivot_key_stride: int, n_pivot_keys: int, queries,
+                      query_offsets, query_stride: int, n_queries: int, leaf_keys, leaf_key_offsets,
+                      leaf_key_stride: int, n_leaf_keys: int, d_key_begin, leaf_values, leaf_value_offsets,
+                      leaf_value_stride: int, leaf_values_bytes: int, d_result, d_query_visits=None,
+                      flags: int = 0, d_metrics=None, d_counts=None, stream=None) -> None:
+    """The launch alone (tkv_amq_get_values), capturable: get_keys_device's arguments and the
+    leaves' values (bytes, offsets or a fixed stride, the buffer's size); d_result: uint8 [32 *
+    n_queries] (abi.VALUE_RESULT_DTYPE records); d_counts: int64 [8] (ValueCounts.counts) or None."""
+    _require_device()
+    st = abi.lib().tkv_amq_get_values(
+        kind, _ptr(filters), _ptr(d_segs), int(n_segs), _ptr(d_nodes), int(n_nodes), _ptr(d_segments),
+        int(n_segments), _ptr(d_children), int(n_children), _ptr(d_flushed_bounds), int(n_flushed_bounds),
+        _ptr(pivot_keys), _ptr(pivot_key_offsets), int(pivot_key_stride), int(n_pivot_keys), _ptr(queries),
+        _ptr(query_offsets), int(query_stride), int(n_queries), _ptr(leaf_keys), _ptr(leaf_key_offsets),
+        int(leaf_key_stride), int(n_leaf_keys), _ptr(d_key_begin), _ptr(leaf_values), _ptr(leaf_value_offsets),
+        int(leaf_value_stride), int(leaf_values_bytes), int(flags), _ptr(d_result), _ptr(d_query_visits),
+        _ptr(d_metrics), _ptr(d_counts), _stream_handle(stream))
+    abi.check(st, "tkv_amq_get_values")
+
+
+def gather_values_device(d_result, n_queries: int, leaf_values, leaf_value_offsets, leaf_value_stride: int,
+                         leaf_values_bytes: int, n_leaf_keys: int, d_out, out_stride: int, d_value_len,
+                         stream=None) -> None:
+    """The launch alone (tkv_amq_gather_values), capturable behind get_values_device: d_out: uint8
+    [n_queries * out_stride]; d_value_len: int32 [n_queries]."""
+    _require_device()
+    st = abi.lib().tkv_amq_gather_values(
+        _ptr(d_result), int(n_queries), _ptr(leaf_values), _ptr(leaf_value_offsets), int(leaf_value_stride),
+        int(leaf_values_bytes), int(n_leaf_keys), _ptr(d_out), int(out_stride), _ptr(d_value_len),
+        _stream_handle(stream))
+    abi.check(st, "tkv_amq_gather_values")
+
+
+def get_values(plan_or_opened, filters, tree: TreeIndex, queries: KeyBatch, leaf_keys: KeyBatch,
+               leaf_values: KeyBatch, *, key_begin=None, check_page_ids: bool = False,
+               want_visits: bool = False, metrics: ProbeMetrics | None = None,
+               counts: ValueCounts | None = None, gather: int | None = None, stream=None) -> ValueResult:
+    """A batch of point lookups from keys to resolved values (tkv_amq_get_values): get_keys'
+    descent, with every found item's packed value (an op byte, then the data; value i belongs to
+    leaf key i, `leaf_values` in either KeyBatch form) folded as the reference's combine_in_place
+    folds it -- ADD_I32 deltas are summed through the older levels and the child until a WRITE or a
+    DELETE resolves them.  gather=out_stride also runs tkv_amq_gather_values behind it: each
+    value's bytes in a slot of out_stride bytes, and its full length.  Nothing is copied back."""
+    torch = _torch()
+    _require_device()
+    plan = plan_or_opened.plan if isinstance(plan_or_opened, OpenedFilters) else plan_or_opened
+    dev = queries.data.device
+    n = plan.n_segs
+    d_kb = None
+    if key_begin is not None:
+        d_kb = (key_begin if hasattr(key_begin, "data_ptr") else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(key_begin, dtype=np.uint64)).view(np.int64))).to(
+                device=dev, dtype=torch.int64).contiguous()
+        if int(d_kb.numel()) != n + 1:
+            raise TkvAmqError(abi.INVALID_ARGUMENT, "get_values: key_begin needs n_segs + 1 entries")
+    if leaf_values.n != leaf_keys.n:
+        raise TkvAmqError(abi.INVALID_ARGUMENT, "get_values: one value per leaf key")
+    d_nodes, d_segments, d_kids, d_bounds, pk = tree.device(dev)
+    nq = queries.n
+    raw = torch.empty(max(nq, 1) * 32, dtype=torch.uint8, device=dev)
+    visits = torch.empty(max(nq, 1), dtype=torch.int32, device=dev) if want_visits else None
+    v_bytes = int(leaf_values.data.numel())
+    get_values_device(plan.kind, filters if n else None, plan.device_segs(dev) if n else None, n, d_nodes,
+                      len(tree.nodes), d_segments, len(tree.segments), d_kids, len(tree.children), d_bounds,
+                      len(tree.flushed_bounds), pk.data, pk.offsets, pk.stride, pk.n, queries.data,
+                      queries.offsets, queries.stride, nq, leaf_keys.data, leaf_keys.offsets,
+                      leaf_keys.stride, leaf_keys.n, d_kb, leaf_values.data, leaf_values.offsets,
+                      leaf_values.stride, v_bytes, raw, visits,
+                      abi.GET_CHECK_PAGE_ID if check_page_ids else 0,
+                      None if metrics is None else metrics.counts, None if counts is None else counts.counts,
+                      stream)
+    slots = lengths = None
+    if gather is not None:
+        slots = torch.empty((max(nq, 1), int(gather)), dtype=torch.uint8, device=dev)
+        lengths = torch.empty(max(nq, 1), dtype=torch.int32, device=dev)
+        gather_values_device(raw, nq, leaf_values.data, leaf_values.offsets, leaf_values.stride, v_bytes,
+                             leaf_values.n, slots, int(gather), lengths, stream)
+        slots, lengths = slots[:nq], lengths[:nq]
+    _hold(stream, d_kb, raw, visits, slots, lengths)
+    rec = raw[:32 * nq].view(torch.int64).view(nq, 4)
+    lc = raw[:32 * nq].view(torch.int32).view(nq, 8)
+    return ValueResult(rec[:, 0], lc[:, 4], lc[:, 5], None if visits is None else visits[:nq], raw, slots, lengths)
+
+
+# ---------------------------------------------------------------------------------------
 # single-leaf API (the reference's per-leaf entry points)
 # ---------------------------------------------------------------------------------------
 @dataclass
