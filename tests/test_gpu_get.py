@@ -554,7 +554,7 @@ def test_a_cycle_ends_after_max_depth_nodes(oracle, amq, torch, kind):
 def launch_cap():
     """kGetMaxGrid workgroups of kGetThreads lanes, read from the source."""
     from turtle_kv_amd import _build
-    with open(os.path.join(_build.HERE, "csrc", "tkv_amq_kernels.hip")) as f:
+    with open(os.path.join(_build.HERE, "csrc", "tkv_amq_read.hip")) as f:
         src = f.read()
     return (int(re.search(r"constexpr uint32_t kGetMaxGrid = (\d+);", src).group(1)),
             int(re.search(r"constexpr uint32_t kGetThreads = (\d+);", src).group(1)))

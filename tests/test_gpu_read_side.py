@@ -671,7 +671,7 @@ def ex_case(oracle, amq, kind):
 @pytest.mark.parametrize("kind", [BLOOM, VQF])
 def test_ex_grid_inputs(oracle, amq, kind):
     c = ex_case(oracle, amq, kind)
-    # probe_grid(n, true) (turtle_kv_amd/csrc/tkv_amq_kernels.hip) caps the grid of the _ex probes at
+    # probe_grid(n, true) (turtle_kv_amd/csrc/tkv_amq_launch.h) caps the grid of the _ex probes at
     # 8,192 workgroups of 256 lanes: more than two grids of queries, so every lane of the strided
     # loops takes a second pass and the first 300 a third, adding to its ProbeTally in each
     assert N_EX > 2 * EX_GRID * EX_WG and len(ex_queries(oracle)) == N_EX

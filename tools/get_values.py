@@ -28,56 +28,21 @@ the compiler's resource report of the get_keys, get_values and gather kernels an
 import argparse
 import json
 import os
-import re
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from bench import SEG_KEYS, segment_counts, sort_segments_device, splitmix_keys16  # noqa: E402
-from get_keys import RESOURCE_KEYS  # noqa: E402
-from walk_paths import N_BOTTOM, VQF_CAP, build_tree, gen_keys, say, spread, step_limit, timed  # noqa: E402
+from walk_paths import (N_BOTTOM, VQF_CAP, build_tree, gen_keys, resource_report, say, spread, step_limit,  # noqa: E402
+                        timed)
 
 DELETE, NOOP, WRITE, ADD = 0, 1, 2, 3
 COMBINED, BAD_COMBINE = 1, 2
 LEAF_LEVEL = 0xFF
 SAMPLE = 4096
 DATA_BYTES, OUT_STRIDE = 100, 128
-
-
-def resource_report(log):
-    """Registers, LDS and scratch of every lookup and gather kernel, from the compiler (the whole
-    kernels unit is compiled for the device: minutes)."""
-    src = os.path.join(ROOT, "turtle_kv_amd", "csrc", "tkv_amq_kernels.hip")
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-c", "-fPIC",
-                            "--cuda-device-only", "-I" + os.path.join(ROOT, "include"),
-                            "-Rpass-analysis=kernel-resource-usage", src, "-o", os.path.join(d, "k.o")],
-                           capture_output=True, text=True, timeout=1200)
-    if r.returncode != 0:
-        sys.exit("resource report: compile failed: " + r.stderr[-400:])
-    names = subprocess.run(["c++filt"], input="\n".join(re.findall(r"Function Name: (\S+)", r.stderr)),
-                           capture_output=True, text=True, check=True).stdout.split("\n")
-    cur, at = None, 0
-    for line in r.stderr.splitlines():
-        if "remark:" not in line:
-            continue
-        text = line.split("remark:", 1)[1].split("[-Rpass")[0].strip()
-        if text.startswith("Function Name:"):
-            if cur:
-                say(log, "resources", json.dumps(cur))
-            wanted = any(s in names[at] for s in ("::get_keys_", "::get_values_", "::gather_values_"))
-            cur = {"kernel": names[at]} if wanted else None
-            at += 1
-        elif cur is not None and ":" in text:
-            k, v = text.split(":", 1)
-            if k.strip() in RESOURCE_KEYS:
-                cur[k.strip()] = v.strip()
-    if cur:
-        say(log, "resources", json.dumps(cur))
 
 
 def mirror(entries, own, value):
@@ -118,8 +83,9 @@ def main():
     log = open(args.log, "w") if args.log else None
     if args.resources_only:
         say(log, "get_values: kernel resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage)")
-        resource_report(log)
-        return
+        # (the read unit alone, tkv_amq_read.hip, compiled for the device)
+        sys.exit(0 if resource_report(log, "tkv_amq_read.hip", ("::get_keys_", "::get_values_", "::gather_values_"),
+                                      timeout=1200) else 1)
     import numpy as np
     import torch
     import turtle_kv_amd as amq

@@ -1,8 +1,10 @@
-"""Two builds of tkv_amq_kernels.hip compared kernel by kernel (profiles/*/kernels.tsv).
+"""Two builds of the library's device code compared kernel by kernel (profiles/*/kernels.tsv).
 
   python tools/isa_compare.py parent.s new.s OUTDIR
 
-Both files from `hipcc -O3 --offload-arch=gfx950 -std=c++17 -Iinclude --cuda-device-only -S`.
+Both files from `hipcc -O3 --offload-arch=gfx950 -std=c++17 -Iinclude --cuda-device-only -S` of
+one unit of turtle_kv_amd/csrc/ (tkv_amq_kernels.hip, tkv_amq_read.hip, ...), or of several units
+with their .s files concatenated: kernels are matched by name, wherever they were compiled.
 Per kernel: the instruction text with comments and directives stripped, local labels without
 their function number (`.LBB12_3` as `.LBB_3`), and the `.amdhsa_*` resource lines.  Writes
 OUTDIR/kernels.tsv (every kernel) and OUTDIR/differing.txt; needs c++filt for the names."""

@@ -21,9 +21,7 @@ JSON line per shape, and the compiler's resource report of the kernels.  Needs a
 import argparse
 import json
 import os
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -31,40 +29,9 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from bench import segment_counts  # noqa: E402
 from open_scan import say, spread, step_limit, timed, INNER  # noqa: E402
+from walk_paths import resource_report  # noqa: E402
 
 VQF_CAP = 32704
-
-
-def resource_report(log):
-    """Registers, LDS and occupancy of the verify kernels, from the compiler."""
-    src = os.path.join(ROOT, "turtle_kv_amd", "csrc", "tkv_amq_kernels.hip")
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-c", "-fPIC",
-                            "--cuda-device-only", "-I" + os.path.join(ROOT, "include"),
-                            "-Rpass-analysis=kernel-resource-usage", src, "-o", os.path.join(d, "k.o")],
-                           capture_output=True, text=True, timeout=1200)
-    if r.returncode != 0:
-        say(log, "resource report: compile failed:", r.stderr[-400:])
-        return
-    cur = {}
-
-    def flush():
-        if cur and "verify_" in cur["kernel"]:
-            say(log, "resources", json.dumps(cur))
-
-    for line in r.stderr.splitlines():
-        if "remark:" not in line:
-            continue
-        text = line.split("remark:", 1)[1].split("[-Rpass")[0].strip()
-        if text.startswith("Function Name:"):
-            flush()
-            cur = {"kernel": text.split(":", 1)[1].strip()}
-        elif ":" in text:
-            k, v = text.split(":", 1)
-            if k.strip() in ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]",
-                             "LDS Size [bytes/block]", "VGPRs Spill", "SGPRs Spill"):
-                cur[k.strip()] = v.strip()
-    flush()
 
 
 def main():
@@ -88,7 +55,8 @@ def main():
     say(log, "verify_members:", amq.abi.version(), "|", torch.cuda.get_device_name(0))
     if not args.no_resources:
         with step_limit(1200, "resource report"):
-            resource_report(log)
+            # (tkv_amq_verify.h is compiled with the builds, in tkv_amq_kernels.hip)
+            resource_report(log, "tkv_amq_kernels.hip", ("verify_",), timeout=1200)
 
     n_all = args.total_keys // 2 * 2
     counts = segment_counts(n_all)

@@ -33,6 +33,7 @@ import ctypes
 import faulthandler
 import json
 import os
+import re
 import statistics
 import subprocess
 import sys
@@ -87,18 +88,26 @@ def spread(v):
             "max_ms": round(max(v), 3), "reps": len(v)}
 
 
-def resource_report(log):
-    """Registers, LDS and scratch of the walk kernels, from the compiler."""
-    src = os.path.join(ROOT, "turtle_kv_amd", "csrc", "tkv_amq_walk.hip")
+RESOURCE_KEYS = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]",
+                 "LDS Size [bytes/block]", "VGPRs Spill", "SGPRs Spill")
+
+
+def resource_report(log, source="tkv_amq_walk.hip", wanted=(), timeout=300):
+    """Registers, LDS and scratch from the compiler, for the kernels of the unit csrc/`source` whose
+    demangled name contains one of `wanted` (none given: every kernel).  The unit is compiled for
+    the device only.  False if it did not compile."""
+    src = os.path.join(ROOT, "turtle_kv_amd", "csrc", source)
     with tempfile.TemporaryDirectory() as d:
         r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-c", "-fPIC",
                             "--cuda-device-only", "-I" + os.path.join(ROOT, "include"),
                             "-Rpass-analysis=kernel-resource-usage", src, "-o", os.path.join(d, "k.o")],
-                           capture_output=True, text=True, timeout=300)
+                           capture_output=True, text=True, timeout=timeout)
     if r.returncode != 0:
         say(log, "resource report: compile failed:", r.stderr[-400:])
-        return
-    cur = {}
+        return False
+    names = subprocess.run(["c++filt"], input="\n".join(re.findall(r"Function Name: (\S+)", r.stderr)),
+                           capture_output=True, text=True, check=True).stdout.split("\n")
+    cur, at = None, 0
     for line in r.stderr.splitlines():
         if "remark:" not in line:
             continue
@@ -106,14 +115,15 @@ def resource_report(log):
         if text.startswith("Function Name:"):
             if cur:
                 say(log, "resources", json.dumps(cur))
-            cur = {"kernel": text.split(":", 1)[1].strip()}
-        elif ":" in text:
+            cur = {"kernel": names[at]} if not wanted or any(w in names[at] for w in wanted) else None
+            at += 1
+        elif cur is not None and ":" in text:
             k, v = text.split(":", 1)
-            if k.strip() in ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]",
-                             "LDS Size [bytes/block]", "VGPRs Spill", "SGPRs Spill"):
+            if k.strip() in RESOURCE_KEYS:
                 cur[k.strip()] = v.strip()
     if cur:
         say(log, "resources", json.dumps(cur))
+    return True
 
 
 # ---------------------------------------------------------------------------------------

@@ -15,18 +15,17 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libtkv_amq.so")
-SOURCES = [os.path.join(HERE, "csrc", "tkv_amq_kernels.hip"),
-           os.path.join(HERE, "csrc", "tkv_amq_open_scan.hip"),
-           os.path.join(HERE, "csrc", "tkv_amq_find.hip"),
-           os.path.join(HERE, "csrc", "tkv_amq_walk.hip"),
-           os.path.join(HERE, "csrc", "tkv_amq_stage.cpp")]
-DEPS = SOURCES + [os.path.join(HERE, "csrc", "tkv_amq_device.h"),
-                  os.path.join(HERE, "csrc", "tkv_amq_key_order.h"),  # (included by tkv_amq_device.h)
-                  os.path.join(HERE, "csrc", "tkv_amq_scan.h"),  # (kernels, open_scan and walk units)
-                  os.path.join(HERE, "csrc", "tkv_amq_tree_walk.h"),  # (kernels and walk units)
-                  os.path.join(HERE, "csrc", "tkv_amq_lds_stride.h"),  # (included by tkv_amq_kernels.hip)
-                  os.path.join(HERE, "csrc", "tkv_amq_verify.h"),  # (included by tkv_amq_kernels.hip)
-                  os.path.join(ROOT, "include", "tkv_amq.h")]
+CSRC = os.path.join(HERE, "csrc")
+SOURCES = [os.path.join(CSRC, "tkv_amq_kernels.hip"),
+           os.path.join(CSRC, "tkv_amq_read.hip"),
+           os.path.join(CSRC, "tkv_amq_open_scan.hip"),
+           os.path.join(CSRC, "tkv_amq_find.hip"),
+           os.path.join(CSRC, "tkv_amq_walk.hip"),
+           os.path.join(CSRC, "tkv_amq_stage.cpp")]
+# what the library is built from: every source and header of csrc/, whichever unit includes it
+# (tests/test_build_deps.py follows the includes), and the public header
+DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip", ".cpp"))) + \
+    [os.path.join(ROOT, "include", "tkv_amq.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC",
          "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include")]

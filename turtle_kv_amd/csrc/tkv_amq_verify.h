@@ -1,6 +1,10 @@
 // tkv_amq_verify.h -- tkv_amq_verify_members: does every key of every leaf pass its own filter?
-// Included at the end of tkv_amq_kernels.hip (it uses that file's hashers, bit ladder, block
-// tests and key-mode dispatch; it is not a translation unit of its own).  DESIGN.md section 13.
+// Included at the end of tkv_amq_kernels.hip; it is not a translation unit of its own.  It uses
+// the hashers and the bit ladder of tkv_amq_hash.h, the block tests of tkv_amq_probe.h
+// (bloom_block_test, vqf_present_at), div_up and as_stream of tkv_amq_launch.h,
+// prefix_inclusive_u64 of tkv_amq_scan.h, and of the build unit itself the VQF build's key
+// buffer and hash (VqfKeyBuf, vqf_key_hash), with_build_key_mode, launch_lds_cap and the leaf LDS
+// budgets, which is why it is compiled there.  DESIGN.md section 13.
 //
 //   verify_init     one lane per leaf: the clamped key range, the flags (no filter, the payload's
 //                   src_page_id against the segment's), the result zeroed, the leaf's unit count
