@@ -68,6 +68,14 @@
  *                           needs_combine() (:279-285) -- OP_ADD_I32 deltas are summed until an
  *                           OP_WRITE or an OP_DELETE resolves them
  *   tkv_amq_gather_values   the resolved values' bytes, one fixed slot per lookup
+ *   tkv_amq_merge_leaves    the leaf update, {BatchUpdate} + {PackedLeafPage} => leaf (tree/
+ *                           subtree.cpp:170-191, 211-231): merge_compact_edits over the update's
+ *                           edits (newer) and the leaf's items (older) -- the stable merge
+ *                           (core/algo/merge_compact_edits.hpp:84-94), run_compact (core/algo/
+ *                           parallel_compact.hpp:80-116) and keep_item (core/algo/decay_to_item.hpp:
+ *                           14-46) -- batched over the leaves of one update, as 16-byte records
+ *   tkv_amq_gather_merged   those records' keys and packed values, as the arrays tkv_amq_build and
+ *                           tkv_amq_get_values take
  *   tkv_amq_open_filters    what KeyQuery::reject_page reads from a loaded filter page instead
  *                           of a plan (tree/key_query.hpp:149-247): check_magic()
  *                           (vqf_filter_page_view.hpp:96-100), src_page_id, block_count,
@@ -967,6 +975,153 @@ int tkv_amq_gather_values(const tkv_amq_value_result* d_result, uint64_t n_queri
                           const uint8_t* leaf_values, const uint64_t* leaf_value_offsets,
                           uint32_t leaf_value_stride, uint64_t leaf_values_bytes, uint64_t n_leaf_keys,
                           uint8_t* d_out, uint32_t out_stride, uint32_t* d_value_len, void* stream);
+
+/* Leaf update on the device: a batch of n_jobs independent two-run merges, one per leaf being
+ * updated -- the reference's {BatchUpdate} + {PackedLeafPage} => leaf (tree/subtree.cpp:170-191,
+ * 211-231), which pushes the update's edits as the NEWER level and the leaf's items as the OLDER one
+ * and runs merge_compact_edits over them (core/algo/merge_compact_edits.hpp:26-148).  Its output is
+ * what tkv_amq_plan / tkv_amq_build and the lookups read, so an update batch becomes new leaves, new
+ * filters and answered lookups without a key or a value leaving the device.
+ * A run (tkv_amq_merge_run, a host struct of device pointers) is n_items items: their keys in the key
+ * forms of tkv_amq_build (key_offsets[n_items + 1] on the device, or key_offsets NULL and the fixed
+ * key_stride), their packed values in the value forms of tkv_amq_get_values (value_offsets[n_items +
+ * 1] or the fixed value_stride, clamped to values_bytes as there), and d_begin[n_jobs + 1] (device):
+ * job j's items are [d_begin[j], d_begin[j + 1]), both ends clamped to n_items, an end below its
+ * begin read as empty (tkv_amq_find_keys' rules).  The two runs' forms are independent.  Ranges of
+ * different jobs are disjoint in every leaf update; so that overlapping ones are defined too, a run
+ * never reads more than n_items items in all: job j reads the first min(its count, n_items - the
+ * counts of the jobs before it) items of its range.
+ * PRECONDITION: each run of each job is in strictly ascending std::string_view order (keys unique
+ * within a run, as in a leaf and in a compacted result set).  On other input the result is what the
+ * procedure below yields: defined, never read or written out of range, and no merge answer (two
+ * candidates may then claim one position of their job, which leaves another of its positions
+ * unwritten).
+ * Per job, with N and O its runs:
+ *  - a NEWER item N[i]: r = the lower bound of its key in O; if r is inside O and O[r]'s key equals
+ *    it (bytes and length), O[r] is its PARTNER.  It emits one candidate:
+ *      no partner                           the item as it is
+ *      a partner, newer op not ADD_I32      the item as it is (an empty value reads as NOOP)
+ *      newer ADD_I32 over WRITE             op WRITE, i32 = a + b modulo 2^32, TKV_AMQ_VALUE_COMBINED
+ *      newer ADD_I32 over DELETE            op WRITE, i32 = a, COMBINED
+ *      newer ADD_I32 over ADD_I32           op ADD_I32, i32 = a + b, COMBINED
+ *      newer ADD_I32 over any other op (NOOP, PAGE_SLICE, unknown, empty): the item unchanged,
+ *                                           TKV_AMQ_VALUE_BAD_COMBINE, bad_combine_count + 1
+ *    with a, b the two values' as_i32() exactly as tkv_amq_get_values defines it by data length
+ *  - an OLDER item O[k]: u = the upper bound of its key in N; if u > 0 and N[u - 1]'s key equals it
+ *    the item is SHADOWED and emits nothing; otherwise it emits itself
+ *  - with TKV_AMQ_MERGE_DECAY_TO_ITEMS a candidate whose resolved op is DELETE, NOOP or none of the
+ *    five defined ops is dropped (decays_to_item, core/value_view.hpp:372-398); without the flag
+ *    every candidate is kept -- leaves keep their tombstones (ResultSet<decay_to_items = false>,
+ *    tree/in_memory_leaf.hpp:35)
+ *  - the kept candidates of job j appear in key order: a newer item at (kept newer items before it)
+ *    + (kept older items before its bound r), an older one at (kept newer items before its bound u)
+ *    + (kept older items before it)
+ * On runs that meet the precondition this IS the reference's merge, run_compact and keep_item.  The
+ * stable merge (merge_compact_edits.hpp:84-94) orders by key, the newer level first among equals; a
+ * key occurs at most once in N and once in O, so a group of equal keys is one item, or N[i] followed
+ * by its partner O[r] -- and the lower bound finds exactly that partner, the upper bound exactly that
+ * shadowing item.  run_compact (core/algo/parallel_compact.hpp:80-116) lets the group's first item
+ * stand and folds the later ones into it with combine while it needs_combine()
+ * (core/value_view.hpp:279-285, 316-335), which is true of ADD_I32 alone: with one later item that
+ * is the table above, and the partner emits nothing of its own.  keep_item
+ * (core/algo/decay_to_item.hpp:14-46) then judges the group's folded value, as the decay rule does.
+ * Groups come out in key order, and the items before a group are the newer ones before N[i] and the
+ * older ones with a smaller key, which are those before r (before u for an older item: every newer
+ * key below it, and none equal to it, lies before u).
+ *  d_out_begin[n_jobs + 1] (device) the exact prefix sums of the jobs' kept counts -- exact whatever
+ *                       out_capacity is (unlike the walk's clamped d_path_begin): the gather and the
+ *                       plan need true counts
+ *  d_items[out_capacity] (device, 16-byte aligned) the records; job j's are d_items[d_out_begin[j] ..
+ *                       d_out_begin[j + 1]); a record at or past out_capacity is not written
+ *  d_needed             (device, 8-byte aligned, or NULL) the total, so a short capacity shows
+ *  d_counts             (device, 8-byte aligned, or NULL) ADDED to, one atomic per non-zero counter
+ *                       per wave; zero it to reset
+ * The output positions are a function of the input: no atomic touches one.
+ * Asynchronous on `stream`: a fixed chain of kernel launches, no allocation, no synchronisation, no
+ * copy; capturable.  n_jobs == 0 is OK and writes d_out_begin[0] = 0 and *d_needed = 0.
+ * tkv_amq_merge_leaves_ws_bytes (host): the workspace the call needs, at least 16, monotone in each
+ * argument, 0 for counts the call refuses.
+ * InvalidArgument, judged before a device is looked for: unknown flag bits; a null run, d_out_begin,
+ * or (n_jobs > 0) d_begin or workspace; n_jobs, either n_items or their sum above 0xffffffff; null
+ * keys with n_items > 0; null values with n_items > 0 and values_bytes > 0; a fixed form (no offsets)
+ * with stride 0, keys or values, either run; a null d_items with out_capacity > 0; d_items not 16-byte
+ * aligned; d_needed or d_counts not 8-byte aligned; a workspace below _ws_bytes or not 16-byte
+ * aligned.  A valid call on a machine without a device returns Unavailable. */
+#define TKV_AMQ_MERGE_DECAY_TO_ITEMS 0x1u
+
+typedef struct tkv_amq_merge_run { /* 64 bytes; a host struct, its pointers device memory */
+  const uint8_t* keys;
+  const uint64_t* key_offsets;   /* n_items + 1 entries, or NULL: the fixed form */
+  const uint8_t* values;
+  const uint64_t* value_offsets; /* n_items + 1 entries, or NULL: the fixed form */
+  const uint64_t* d_begin;       /* n_jobs + 1 entries (tkv_amq_gather_merged does not read it) */
+  uint64_t n_items;
+  uint64_t values_bytes;
+  uint32_t key_stride;
+  uint32_t value_stride;
+} tkv_amq_merge_run;
+
+typedef struct tkv_amq_merge_item { /* 16 bytes */
+  uint64_t src;      /* bit 63: the run (0 newer, 1 older); bits 0..62: the item's global index in that run's arrays */
+  int32_t i32;       /* COMBINED: the folded integer; else 0 */
+  uint8_t op;        /* the resolved op (TKV_AMQ_OP_*; an empty value: NOOP) */
+  uint8_t flags;     /* TKV_AMQ_VALUE_COMBINED | TKV_AMQ_VALUE_BAD_COMBINE */
+  uint16_t reserved; /* 0 */
+} tkv_amq_merge_item;
+
+typedef struct tkv_amq_merge_counts { /* 56 bytes, u64 each, ADDED to with atomics (zero to reset) */
+  uint64_t newer_count;       /* newer items read */
+  uint64_t older_count;       /* older items read */
+  uint64_t pair_count;        /* shadowed older items */
+  uint64_t combined_count;    /* candidates folded from two items */
+  uint64_t bad_combine_count; /* newer ADD_I32 over an item that cannot be combined */
+  uint64_t dropped_count;     /* candidates dropped by decay */
+  uint64_t out_count;         /* candidates kept */
+} tkv_amq_merge_counts;
+
+uint64_t tkv_amq_merge_leaves_ws_bytes(uint64_t n_jobs, uint64_t n_newer, uint64_t n_older);
+int tkv_amq_merge_leaves(const tkv_amq_merge_run* newer, const tkv_amq_merge_run* older, uint64_t n_jobs,
+                         uint32_t flags, uint64_t* d_out_begin, tkv_amq_merge_item* d_items,
+                         uint64_t out_capacity, uint64_t* d_needed, tkv_amq_merge_counts* d_counts,
+                         void* d_workspace, uint64_t workspace_bytes, void* stream);
+
+/* The bytes of a batch of tkv_amq_merge_leaves records, as arrays the other entry points take: the
+ * merged items' keys (for tkv_amq_plan / tkv_amq_build / the lookups, with d_out_begin as their
+ * d_key_begin) and their packed values (for tkv_amq_get_values).
+ * n_out, the records gathered, is read on the device: min(d_out_begin[n_jobs], out_capacity,
+ * newer->n_items + older->n_items) -- no host read sits between the two calls.  The runs are those of
+ * the merge (d_begin is not read).  A record whose src index is at or past its run's n_items is caller
+ * memory trusted no further: it gives an empty key and an empty value.
+ *  keys    out_key_stride > 0: the fixed form, key p at d_out_keys + p * out_key_stride -- only when
+ *          both runs' keys are fixed with that same stride (an untrusted record's slot is left as it
+ *          is); out_key_stride == 0: the offsets form, d_out_key_offsets[n_out + 1] written by the call
+ *  values  always the offsets form, d_out_value_offsets[n_out + 1] written by the call.  A COMBINED
+ *          record writes 5 bytes, the op byte and i32 little-endian; every other record its source
+ *          value's bytes verbatim under tkv_amq_get_values' clamps (an empty value stays empty)
+ * Offsets are exact whatever the capacities: an item's bytes are written only if the item ends at or
+ * below out_keys_capacity / out_values_capacity (bytes), and d_needed_bytes[0], [1] (device, or NULL)
+ * report the keys' and the values' totals.  tkv_amq_merge_values_bound (host) bounds the values' total
+ * before the merge has run: newer_bytes + older_bytes + 4 * n_newer, as a combined value replaces a
+ * non-empty newer value and is 5 bytes.
+ * Sixteen lanes move one item, eight bytes per lane and step, with a byte tail where the destination
+ * is not 8-byte aligned.  Asynchronous on `stream`, no allocation, no
+ * synchronisation; capturable behind tkv_amq_merge_leaves.  tkv_amq_gather_merged_ws_bytes (host): at
+ * least 16, monotone.
+ * InvalidArgument, judged before a device is looked for: a null run, d_out_begin, d_out_value_offsets
+ * or workspace; n_jobs or either n_items or their sum above 0xffffffff; the runs' checks of
+ * tkv_amq_merge_leaves (null keys, null values, stride 0); a null d_items with out_capacity > 0, or
+ * not 16-byte aligned; out_key_stride > 0 with a run in the offsets form or of another stride;
+ * out_key_stride == 0 with a null d_out_key_offsets; a null d_out_keys / d_out_values with its
+ * capacity > 0; d_out_key_offsets, d_out_value_offsets or d_needed_bytes not 8-byte aligned; a
+ * workspace below _ws_bytes or not 16-byte aligned.  A valid call without a device: Unavailable. */
+uint64_t tkv_amq_merge_values_bound(uint64_t newer_bytes, uint64_t older_bytes, uint64_t n_newer);
+uint64_t tkv_amq_gather_merged_ws_bytes(uint64_t out_capacity);
+int tkv_amq_gather_merged(const tkv_amq_merge_item* d_items, const uint64_t* d_out_begin, uint64_t n_jobs,
+                          uint64_t out_capacity, const tkv_amq_merge_run* newer, const tkv_amq_merge_run* older,
+                          uint8_t* d_out_keys, uint32_t out_key_stride, uint64_t* d_out_key_offsets,
+                          uint64_t out_keys_capacity, uint8_t* d_out_values, uint64_t* d_out_value_offsets,
+                          uint64_t out_values_capacity, uint64_t* d_needed_bytes, void* d_workspace,
+                          uint64_t workspace_bytes, void* stream);
 
 /* Open built filters without a plan (a store restarting on a checkpoint, filter pages received
  * from elsewhere): reconstructs and validates one segment per filter from the filter bytes on

@@ -24,6 +24,8 @@
 //                                                                          TreeIndex::get_host, KeyQuery::get_keys
 //   ... with combine_in_place             core/value_view.hpp:316-361, core/packed_key_value.hpp:18-23
 //                                                                          TreeIndex::get_values_host, KeyQuery::get_values
+//   {BatchUpdate} + {PackedLeafPage}      tree/subtree.cpp:170-231, core/algo/merge_compact_edits.hpp:26-148
+//                                                                          merge_leaves
 //
 // The single-leaf functions take the leaf's keys as host string views (the reference's
 // `items` range of EditView keys, tombstones included) and fill a host page payload
@@ -2022,5 +2024,82 @@ class KeyQuery
  private:
   std::vector<std::string_view> keys_;
 };
+
+// ---------------------------------------------------------------------------------------
+// leaf update: {BatchUpdate} + {PackedLeafPage} => leaf (tree/subtree.cpp:170-191, 211-231) for a
+// batch of leaves, on the device (tkv_amq_merge_leaves, tkv_amq_gather_merged)
+// ---------------------------------------------------------------------------------------
+// The merged leaves, device-resident: what FilterBatchBuilder, KeyQuery::verify_members and
+// KeyQuery::get_values take as leaf keys, leaf values and key_begin.
+struct MergedLeaves {
+  DeviceBuffer items;          // tkv_amq_merge_item [n_items]
+  DeviceBuffer out_begin;      // u64 [n_jobs + 1]
+  DeviceBuffer keys, key_offsets;      // key_stride > 0: fixed slots, key_offsets unused; else u64 [n_items + 1]
+  DeviceBuffer values, value_offsets;  // packed values and u64 [n_items + 1]
+  u32 key_stride = 0;
+  std::vector<u64> begin;      // out_begin on the host: leaf j holds items [begin[j], begin[j + 1])
+  u64 n_items = 0, key_bytes = 0, value_bytes = 0;
+  tkv_amq_merge_counts counts{};
+};
+
+// Job j merges the update's items newer.d_begin[j .. j + 1) over the leaf's items older.d_begin[j .. j + 1),
+// each run strictly ascending: the newer item of a key stands, an ADD_I32 is folded with the older
+// item, and with decay_to_items tombstones and no-ops are dropped (a leaf keeps them:
+// ResultSet<decay_to_items = false>, tree/in_memory_leaf.hpp:35).  The outputs are sized from the
+// inputs, so nothing is truncated; the counts and out_begin are copied back.
+inline Status merge_leaves(const tkv_amq_merge_run& newer, const tkv_amq_merge_run& older, u64 n_jobs,
+                           bool decay_to_items, MergedLeaves& out)
+{
+  out.begin.assign(1, 0);
+  out.n_items = out.key_bytes = out.value_bytes = 0;
+  out.counts = tkv_amq_merge_counts{};
+  const u64 ws_bytes = tkv_amq_merge_leaves_ws_bytes(n_jobs, newer.n_items, older.n_items);
+  if (ws_bytes == 0) return Status::from(TKV_AMQ_INVALID_ARGUMENT, "merge_leaves: too many jobs or items");
+  if ((!newer.key_offsets && !newer.key_stride) || (!older.key_offsets && !older.key_stride) ||
+      (!newer.value_offsets && !newer.value_stride) || (!older.value_offsets && !older.value_stride))
+    return Status::from(TKV_AMQ_INVALID_ARGUMENT, "merge_leaves: a fixed form with stride 0");
+  if (tkv_amq_device_count() == 0) return Status::from(TKV_AMQ_UNAVAILABLE, "no HIP device");
+  const u64 cap = newer.n_items + older.n_items;
+  const bool fixed = !newer.key_offsets && !older.key_offsets && newer.key_stride == older.key_stride;
+  out.key_stride = fixed ? newer.key_stride : 0;
+  auto key_bytes_of = [](const tkv_amq_merge_run& r, u64& bytes) {
+    bytes = r.n_items * r.key_stride;
+    if (!r.key_offsets || r.n_items == 0) return true;
+    return hipMemcpy(&bytes, r.key_offsets + r.n_items, 8, hipMemcpyDeviceToHost) == hipSuccess;
+  };
+  u64 nk = 0, ok = 0;
+  if (!key_bytes_of(newer, nk) || !key_bytes_of(older, ok)) return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy key offsets");
+  const u64 k_cap = nk + ok;
+  const u64 v_cap = tkv_amq_merge_values_bound(newer.values_bytes, older.values_bytes, newer.n_items);
+  const u64 gather_ws = tkv_amq_gather_merged_ws_bytes(cap);
+  DeviceBuffer ws, tallies;
+  if (!ws.resize(std::max(ws_bytes, gather_ws)) || !tallies.resize(sizeof(tkv_amq_merge_counts)) ||
+      !out.items.resize(sizeof(tkv_amq_merge_item) * cap) || !out.out_begin.resize(8 * (n_jobs + 1)) ||
+      !out.keys.resize(k_cap) || (!fixed && !out.key_offsets.resize(8 * (cap + 1))) || !out.values.resize(v_cap) ||
+      !out.value_offsets.resize(8 * (cap + 1)))
+    return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+  if (hipMemset(tallies.get(), 0, sizeof(tkv_amq_merge_counts)) != hipSuccess)
+    return Status::from(TKV_AMQ_INTERNAL, "hipMemset counters");
+  int st = tkv_amq_merge_leaves(&newer, &older, n_jobs, decay_to_items ? TKV_AMQ_MERGE_DECAY_TO_ITEMS : 0u,
+                                out.out_begin.get<u64>(), out.items.get<tkv_amq_merge_item>(), cap, nullptr,
+                                tallies.get<tkv_amq_merge_counts>(), ws.get(), ws.size(), nullptr);
+  if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_merge_leaves");
+  st = tkv_amq_gather_merged(out.items.get<tkv_amq_merge_item>(), out.out_begin.get<u64>(), n_jobs, cap, &newer,
+                             &older, out.keys.get(), out.key_stride, fixed ? nullptr : out.key_offsets.get<u64>(),
+                             k_cap, out.values.get(), out.value_offsets.get<u64>(), v_cap, nullptr, ws.get(),
+                             ws.size(), nullptr);
+  if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_gather_merged");
+  out.begin.assign(n_jobs + 1, 0);
+  // (blocking copies on the null stream: they wait for the merge and the gather)
+  if (hipMemcpy(out.begin.data(), out.out_begin.get(), 8 * (n_jobs + 1), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&out.counts, tallies.get(), sizeof(out.counts), hipMemcpyDeviceToHost) != hipSuccess)
+    return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy merge results");
+  out.n_items = out.begin.back();
+  out.key_bytes = out.n_items * out.key_stride;
+  if ((!fixed && hipMemcpy(&out.key_bytes, out.key_offsets.get<u64>() + out.n_items, 8, hipMemcpyDeviceToHost) != hipSuccess) ||
+      hipMemcpy(&out.value_bytes, out.value_offsets.get<u64>() + out.n_items, 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy merge sizes");
+  return OkStatus();
+}
 
 }  // namespace turtle_kv_amd

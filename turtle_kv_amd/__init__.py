@@ -19,7 +19,9 @@ from .filters import (BoolStatus, FilterPage, FilterPlan, KeyBatch, KeyQuery, Pa
                       find_keys_device, FindResult, FindCounts, TreeIndex, WalkResult, walk_paths,
                       walk_paths_device, walk_paths_workspace_bytes, get_keys, get_keys_device,
                       GetResult, GetCounts, get_values, get_values_device, gather_values_device,
-                      ValueResult, ValueCounts)
+                      ValueResult, ValueCounts, merge_leaves, merge_leaves_device,
+                      gather_merged_device, merge_run, merge_leaves_workspace_bytes,
+                      gather_merged_workspace_bytes, merge_values_bound, MergeResult, MergeCounts)
 
 __all__ = [
     "abi", "BLOOM", "VQF", "TkvAmqError", "BoolStatus", "FilterPage", "FilterPlan", "KeyBatch",
@@ -37,4 +39,7 @@ __all__ = [
     "TreeIndex", "WalkResult", "walk_paths", "walk_paths_device", "walk_paths_workspace_bytes",
     "get_keys", "get_keys_device", "GetResult", "GetCounts",
     "get_values", "get_values_device", "gather_values_device", "ValueResult", "ValueCounts",
+    "merge_leaves", "merge_leaves_device", "gather_merged_device", "merge_run",
+    "merge_leaves_workspace_bytes", "gather_merged_workspace_bytes", "merge_values_bound", "MergeResult",
+    "MergeCounts",
 ]

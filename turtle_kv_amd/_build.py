@@ -21,6 +21,7 @@ SOURCES = [os.path.join(CSRC, "tkv_amq_kernels.hip"),
            os.path.join(CSRC, "tkv_amq_open_scan.hip"),
            os.path.join(CSRC, "tkv_amq_find.hip"),
            os.path.join(CSRC, "tkv_amq_walk.hip"),
+           os.path.join(CSRC, "tkv_amq_merge.hip"),
            os.path.join(CSRC, "tkv_amq_stage.cpp")]
 # what the library is built from: every source and header of csrc/, whichever unit includes it
 # (tests/test_build_deps.py follows the includes), and the public header

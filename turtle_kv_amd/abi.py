@@ -101,6 +101,8 @@ EXPORTS = [
     "tkv_amq_walk_paths_ws_bytes", "tkv_amq_walk_paths",
     "tkv_amq_get_keys",
     "tkv_amq_get_values", "tkv_amq_gather_values",
+    "tkv_amq_merge_leaves_ws_bytes", "tkv_amq_merge_leaves", "tkv_amq_merge_values_bound",
+    "tkv_amq_gather_merged_ws_bytes", "tkv_amq_gather_merged",
 ]
 
 # tkv_amq_build_route: TKV_AMQ_ROUTE_* (a Bloom batch's route, or a VQF batch's decide stage),
@@ -173,6 +175,28 @@ assert VALUE_COUNTS_DTYPE.itemsize == 64
 OP_DELETE, OP_NOOP, OP_WRITE, OP_ADD_I32, OP_PAGE_SLICE = range(5)
 OP_NONE = 0xFF             # `op` of a lookup that took no item
 VALUE_COMBINED, VALUE_BAD_COMBINE = 0x1, 0x2
+
+# tkv_amq_merge_leaves: its flag (TKV_AMQ_MERGE_DECAY_TO_ITEMS), tkv_amq_merge_item (16 bytes),
+# tkv_amq_merge_counts (56 bytes) and the run bit of a record's src
+MERGE_DECAY_TO_ITEMS = 0x1
+MERGE_ITEM_DTYPE = np.dtype([("src", "<u8"), ("i32", "<i4"), ("op", "u1"), ("flags", "u1"), ("reserved", "<u2")])
+assert MERGE_ITEM_DTYPE.itemsize == 16
+MERGE_COUNTS_FIELDS = ("newer_count", "older_count", "pair_count", "combined_count", "bad_combine_count",
+                       "dropped_count", "out_count")
+MERGE_COUNTS_DTYPE = np.dtype([(n, "<u8") for n in MERGE_COUNTS_FIELDS])
+assert MERGE_COUNTS_DTYPE.itemsize == 56
+MERGE_SRC_OLDER = 1 << 63
+
+
+class MergeRun(ctypes.Structure):
+    """tkv_amq_merge_run (64 bytes): one side of a merge, a host struct of device pointers."""
+    _fields_ = [("keys", ctypes.c_void_p), ("key_offsets", ctypes.c_void_p), ("values", ctypes.c_void_p),
+                ("value_offsets", ctypes.c_void_p), ("d_begin", ctypes.c_void_p),
+                ("n_items", ctypes.c_uint64), ("values_bytes", ctypes.c_uint64),
+                ("key_stride", ctypes.c_uint32), ("value_stride", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(MergeRun) == 64
 
 
 # tkv_amq_walk_paths: the flat tree (tkv_amq_tree_node / _segment / _child) and its limits
@@ -362,6 +386,19 @@ def lib(build_if_missing: bool = True):
     if hasattr(L, "tkv_amq_gather_values"):
         L.tkv_amq_gather_values.restype = i32
         L.tkv_amq_gather_values.argtypes = [vp, u64, vp, vp, u32, u64, u64, vp, u32, vp, vp]
+    if hasattr(L, "tkv_amq_merge_leaves"):
+        prun = ctypes.POINTER(MergeRun)
+        L.tkv_amq_merge_leaves_ws_bytes.restype = u64
+        L.tkv_amq_merge_leaves_ws_bytes.argtypes = [u64, u64, u64]
+        L.tkv_amq_merge_leaves.restype = i32
+        L.tkv_amq_merge_leaves.argtypes = [prun, prun, u64, u32, vp, vp, u64, vp, vp, vp, u64, vp]
+        L.tkv_amq_merge_values_bound.restype = u64
+        L.tkv_amq_merge_values_bound.argtypes = [u64, u64, u64]
+        L.tkv_amq_gather_merged_ws_bytes.restype = u64
+        L.tkv_amq_gather_merged_ws_bytes.argtypes = [u64]
+        L.tkv_amq_gather_merged.restype = i32
+        L.tkv_amq_gather_merged.argtypes = [vp, vp, u64, u64, prun, prun, vp, u32, vp, u64, vp, vp, u64, vp,
+                                            vp, u64, vp]
     if hasattr(L, "tkv_amq_bloom_route"):
         L.tkv_amq_bloom_route_ws_bytes.restype = u64
         L.tkv_amq_bloom_route_ws_bytes.argtypes = [u64, u32]

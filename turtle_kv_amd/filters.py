@@ -1502,6 +1502,163 @@ def get_values(plan_or_opened, filters, tree: TreeIndex, queries: KeyBatch, leaf
 
 
 # ---------------------------------------------------------------------------------------
+# leaf update: a batch of two-run merges (the update's edits over the leaves' items) on the device
+# ---------------------------------------------------------------------------------------
+class MergeCounts:
+    """Device-side tkv_amq_merge_counts that merge_leaves launches add to; `collect()` reads them."""
+
+    def __init__(self, device=None):
+        torch = _torch()
+        self.counts = torch.zeros(len(abi.MERGE_COUNTS_FIELDS), dtype=torch.int64, device=device or "cuda")
+
+    def reset(self) -> None:
+        self.counts.zero_()
+
+    def collect(self) -> dict:
+        return dict(zip(abi.MERGE_COUNTS_FIELDS, (int(v) for v in self.counts.cpu().tolist())))
+
+
+def merge_run(keys: KeyBatch, values: KeyBatch, d_begin=None) -> abi.MergeRun:
+    """tkv_amq_merge_run of one side: its keys and its packed values (value i belongs to key i, either
+    in either KeyBatch form) and, for the merge, d_begin (int64 [n_jobs + 1] on the device).  The
+    struct holds addresses only: the caller keeps the tensors alive."""
+    if values.n != keys.n:
+        raise TkvAmqError(abi.INVALID_ARGUMENT, "merge_run: one value per key")
+
+    def addr(t):
+        return None if t is None or int(t.numel()) == 0 else t.data_ptr()
+
+    return abi.MergeRun(addr(keys.data), addr(keys.offsets), addr(values.data), addr(values.offsets),
+                        addr(d_begin), keys.n, int(values.data.numel()), int(keys.stride), int(values.stride))
+
+
+def merge_leaves_workspace_bytes(n_jobs: int, n_newer: int, n_older: int) -> int:
+    """tkv_amq_merge_leaves_ws_bytes (0: counts the call refuses)."""
+    return int(abi.lib().tkv_amq_merge_leaves_ws_bytes(int(n_jobs), int(n_newer), int(n_older)))
+
+
+def gather_merged_workspace_bytes(out_capacity: int) -> int:
+    """tkv_amq_gather_merged_ws_bytes."""
+    return int(abi.lib().tkv_amq_gather_merged_ws_bytes(int(out_capacity)))
+
+
+def merge_values_bound(newer_bytes: int, older_bytes: int, n_newer: int) -> int:
+    """tkv_amq_merge_values_bound: the merged values' bytes at most."""
+    return int(abi.lib().tkv_amq_merge_values_bound(int(newer_bytes), int(older_bytes), int(n_newer)))
+
+
+def merge_leaves_device(newer: abi.MergeRun, older: abi.MergeRun, n_jobs: int, d_out_begin, d_items,
+                        out_capacity: int, workspace, d_needed=None, flags: int = 0, d_counts=None,
+                        stream=None) -> None:
+    """The launches alone (tkv_amq_merge_leaves), capturable: the two runs (merge_run), d_out_begin:
+    int64 [n_jobs + 1]; d_items: uint8 [16 * out_capacity] (abi.MERGE_ITEM_DTYPE records); workspace:
+    uint8 [merge_leaves_workspace_bytes]; d_needed: int64 [1] or None; d_counts: int64 [7]
+    (MergeCounts.counts) or None."""
+    _require_device()
+    st = abi.lib().tkv_amq_merge_leaves(
+        ctypes.byref(newer), ctypes.byref(older), int(n_jobs), int(flags), _ptr(d_out_begin), _ptr(d_items),
+        int(out_capacity), _ptr(d_needed), _ptr(d_counts), _ptr(workspace),
+        0 if workspace is None else int(workspace.numel()), _stream_handle(stream))
+    abi.check(st, "tkv_amq_merge_leaves")
+
+
+def gather_merged_device(d_items, d_out_begin, n_jobs: int, out_capacity: int, newer: abi.MergeRun,
+                         older: abi.MergeRun, d_out_keys, out_key_stride: int, d_out_key_offsets,
+                         out_keys_capacity: int, d_out_values, d_out_value_offsets, out_values_capacity: int,
+                         workspace, d_needed_bytes=None, stream=None) -> None:
+    """The launches alone (tkv_amq_gather_merged), capturable behind merge_leaves_device: the records'
+    keys (fixed slots of out_key_stride bytes, or with out_key_stride 0 bytes and d_out_key_offsets:
+    int64 [out_capacity + 1]) and values (bytes and d_out_value_offsets); capacities in bytes;
+    d_needed_bytes: int64 [2] or None."""
+    _require_device()
+    st = abi.lib().tkv_amq_gather_merged(
+        _ptr(d_items), _ptr(d_out_begin), int(n_jobs), int(out_capacity), ctypes.byref(newer),
+        ctypes.byref(older), _ptr(d_out_keys), int(out_key_stride), _ptr(d_out_key_offsets),
+        int(out_keys_capacity), _ptr(d_out_values), _ptr(d_out_value_offsets), int(out_values_capacity),
+        _ptr(d_needed_bytes), _ptr(workspace), 0 if workspace is None else int(workspace.numel()),
+        _stream_handle(stream))
+    abi.check(st, "tkv_amq_gather_merged")
+
+
+@dataclass
+class MergeResult:
+    """What merge_leaves leaves on the device: the merged items' `keys` and packed `values` (KeyBatch
+    each: the keys fixed when both inputs were fixed with one stride, else variable; the values
+    variable), `out_begin` (int64 [n_jobs + 1]: job j's items are [out_begin[j], out_begin[j + 1]),
+    the d_key_begin of a plan, a build or a lookup over them), `items` (uint8 [16 * n_out],
+    abi.MERGE_ITEM_DTYPE records) and `counts`, this call's tkv_amq_merge_counts as a dict."""
+    keys: KeyBatch
+    values: KeyBatch
+    out_begin: object
+    items: object = field(default=None, repr=False)
+    counts: dict = field(default_factory=dict)
+
+    def records(self) -> np.ndarray:
+        """The records on the host (a copy; synchronises)."""
+        return self.items.cpu().numpy().view(abi.MERGE_ITEM_DTYPE)
+
+
+def _begin_tensor(begin, dev, what: str):
+    torch = _torch()
+    t = (begin if hasattr(begin, "data_ptr") else torch.from_numpy(
+        np.ascontiguousarray(np.asarray(begin, dtype=np.uint64)).view(np.int64)))
+    t = t.to(device=dev, dtype=torch.int64).contiguous()
+    if int(t.numel()) < 1:
+        raise TkvAmqError(abi.INVALID_ARGUMENT, f"merge_leaves: {what} needs n_jobs + 1 entries")
+    return t
+
+
+def merge_leaves(newer: KeyBatch, newer_values: KeyBatch, newer_begin, older: KeyBatch, older_values: KeyBatch,
+                 older_begin, *, decay: bool = False, stream=None) -> MergeResult:
+    """The leaf update of a batch of leaves (tkv_amq_merge_leaves, then tkv_amq_gather_merged): job j
+    merges the update's items [newer_begin[j], newer_begin[j + 1]) over the leaf's items
+    [older_begin[j], older_begin[j + 1]) -- each run strictly ascending -- as the reference's
+    merge_compact_edits does: the newer item of a key stands, an ADD_I32 is folded with the older
+    item, and with decay=True tombstones and no-ops are dropped (a leaf keeps them).  The outputs are
+    sized from the inputs (every item kept), so nothing is truncated; the record count and `counts`
+    are read back, which synchronises."""
+    torch = _torch()
+    _require_device()
+    dev = older.data.device
+    d_nb = _begin_tensor(newer_begin, dev, "newer_begin")
+    d_ob = _begin_tensor(older_begin, dev, "older_begin")
+    if d_nb.numel() != d_ob.numel():
+        raise TkvAmqError(abi.INVALID_ARGUMENT, "merge_leaves: the begin arrays differ in length")
+    n_jobs = int(d_nb.numel()) - 1
+    rn, ro = merge_run(newer, newer_values, d_nb), merge_run(older, older_values, d_ob)
+    cap = newer.n + older.n
+    ws_bytes = max(merge_leaves_workspace_bytes(n_jobs, newer.n, older.n), gather_merged_workspace_bytes(cap))
+    if ws_bytes == 0:
+        raise TkvAmqError(abi.INVALID_ARGUMENT, "merge_leaves: too many jobs or items")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out_begin = torch.empty(n_jobs + 1, dtype=torch.int64, device=dev)
+    items = torch.empty(max(cap, 1) * 16, dtype=torch.uint8, device=dev)
+    counts = MergeCounts(dev)
+    merge_leaves_device(rn, ro, n_jobs, out_begin, items, cap, ws, None,
+                        abi.MERGE_DECAY_TO_ITEMS if decay else 0, counts.counts, stream)
+    fixed = newer.offsets is None and older.offsets is None and newer.stride == older.stride
+    k_cap = cap * newer.stride if fixed else \
+        (newer.n * newer.stride if newer.offsets is None else int(newer.data.numel())) + \
+        (older.n * older.stride if older.offsets is None else int(older.data.numel()))
+    v_cap = merge_values_bound(int(newer_values.data.numel()), int(older_values.data.numel()), newer.n)
+    out_keys = torch.empty(max(k_cap, 1), dtype=torch.uint8, device=dev)
+    out_vals = torch.empty(max(v_cap, 1), dtype=torch.uint8, device=dev)
+    k_offs = None if fixed else torch.empty(cap + 1, dtype=torch.int64, device=dev)
+    v_offs = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+    gather_merged_device(items, out_begin, n_jobs, cap, rn, ro, out_keys, newer.stride if fixed else 0, k_offs,
+                         k_cap, out_vals, v_offs, v_cap, ws, None, stream)
+    _hold(stream, d_nb, d_ob, ws, out_begin, items, out_keys, out_vals, k_offs, v_offs, counts.counts)
+    (stream if stream is not None else torch.cuda.current_stream()).synchronize()
+    n_out = int(out_begin[n_jobs].item())
+    if fixed:
+        keys = KeyBatch.fixed(out_keys[:n_out * newer.stride].view(n_out, newer.stride))
+    else:
+        keys = KeyBatch.variable(out_keys, k_offs[:n_out + 1])
+    return MergeResult(keys, KeyBatch.variable(out_vals, v_offs[:n_out + 1]), out_begin, items[:16 * n_out],
+                       counts.collect())
+
+
+# ---------------------------------------------------------------------------------------
 # single-leaf API (the reference's per-leaf entry points)
 # ---------------------------------------------------------------------------------------
 @dataclass
