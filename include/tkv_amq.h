@@ -76,6 +76,12 @@
  *                           14-46) -- batched over the leaves of one update, as 16-byte records
  *   tkv_amq_gather_merged   those records' keys and packed values, as the arrays tkv_amq_build and
  *                           tkv_amq_get_values take
+ *   tkv_amq_merge_levels    merge_compact_edits over K levels (core/algo/merge_compact_edits.hpp:
+ *                           26-148, one MergeCompactor::push_level per level): the node path's
+ *                           merge, the incoming batch and every update-buffer level it collapses
+ *                           (InMemoryNode::push_levels_to_merge, tree/in_memory_node.cpp:827-866),
+ *                           up to 8 runs in one call, batched over key ranges, as the same records
+ *   tkv_amq_gather_levels   tkv_amq_gather_merged over that table of runs
  *   tkv_amq_open_filters    what KeyQuery::reject_page reads from a loaded filter page instead
  *                           of a plan (tree/key_query.hpp:149-247): check_magic()
  *                           (vqf_filter_page_view.hpp:96-100), src_page_id, block_count,
@@ -1118,6 +1124,102 @@ uint64_t tkv_amq_merge_values_bound(uint64_t newer_bytes, uint64_t older_bytes, 
 uint64_t tkv_amq_gather_merged_ws_bytes(uint64_t out_capacity);
 int tkv_amq_gather_merged(const tkv_amq_merge_item* d_items, const uint64_t* d_out_begin, uint64_t n_jobs,
                           uint64_t out_capacity, const tkv_amq_merge_run* newer, const tkv_amq_merge_run* older,
+                          uint8_t* d_out_keys, uint32_t out_key_stride, uint64_t* d_out_key_offsets,
+                          uint64_t out_keys_capacity, uint8_t* d_out_values, uint64_t* d_out_value_offsets,
+                          uint64_t out_values_capacity, uint64_t* d_needed_bytes, void* d_workspace,
+                          uint64_t workspace_bytes, void* stream);
+
+/* The node merge on the device: a batch of n_jobs independent K-way merges of sorted runs -- the
+ * reference's merge_compact_edits over a slice of K segments (core/algo/merge_compact_edits.hpp:
+ * 26-148), one MergeCompactor::push_level per level.  The leaf cases push two levels (tree/subtree.cpp:
+ * 182-184, 221-223, tkv_amq_merge_leaves); the node path pushes the incoming batch and every
+ * update-buffer level it is about to collapse (InMemoryNode::push_levels_to_merge, tree/
+ * in_memory_node.cpp:827-866, from the insert at :289-303 and the flushes and compactions at :407,
+ * :454), up to TreeOptions::kMaxLevels + 1 = 7 runs.  One call ranks every item once against every
+ * other run, where a chain of K - 1 tkv_amq_merge_leaves / tkv_amq_gather_merged calls re-materialises
+ * every surviving byte K - 1 times.
+ * `runs` is a HOST array of n_runs tkv_amq_merge_run, 1 <= n_runs <= TKV_AMQ_MERGE_MAX_RUNS, runs[0]
+ * the NEWEST; each run has its own key form, value form and d_begin[n_jobs + 1].  Job j merges items
+ * [d_begin[j], d_begin[j + 1]) of every run (a node merge: one pivot's key range; a leaf update: one
+ * leaf), the ranges clamped exactly as tkv_amq_merge_leaves clamps them: both ends to n_items, an end
+ * below its begin empty, and job j reads the first min(its count, n_items - the counts of the jobs
+ * before it) items of its range, so a run never reads more items in all than it holds.
+ * PRECONDITION: within a job each run is in strictly ascending std::string_view order.  On other
+ * input the result is what the procedure yields: every search stays inside its job's range, every
+ * position inside the job's output range, nothing is read or written out of range.
+ * Per job: a GROUP is its items that share a key (bytes and length) -- on sorted input at most one
+ * per run, ordered by run index by the stable merge (the pairwise merges of adjacent segments,
+ * merge_compact_edits.hpp:53-107, are each stable with src_0 first, so level order survives).  The
+ * group's HEAD is its item in the newest run that holds the key; every other item of the group is
+ * SHADOWED and emits nothing.
+ *  - an item of run s: in each newer run t < s, u = the upper bound of its key; if u > 0 and the item
+ *    before u equals it, the item is shadowed.  Otherwise it is a head: in each older run t > s, r =
+ *    the lower bound of its key; the item at r, if it equals the key, is a PARTNER
+ *  - the head's value is folded through its partners from newer to older WHILE the accumulated op is
+ *    ADD_I32 (run_compact, core/algo/parallel_compact.hpp:92-100; needs_combine() is true of ADD_I32
+ *    alone):
+ *      over WRITE      op WRITE, i32 = the sum modulo 2^32, TKV_AMQ_VALUE_COMBINED
+ *      over DELETE     op WRITE, i32 unchanged, COMBINED
+ *      over ADD_I32    i32 = the sum, COMBINED
+ *      over any other (NOOP, PAGE_SLICE, unknown, empty): the value unchanged, TKV_AMQ_VALUE_
+ *                      BAD_COMBINE, bad_combine_count + 1 -- and the fold goes on to the next older
+ *                      partner, the value still being an ADD_I32
+ *    integers read by as_i32() exactly as tkv_amq_get_values and tkv_amq_merge_leaves read them; both
+ *    flags may be set on one record
+ *  - with TKV_AMQ_MERGE_DECAY_TO_ITEMS a group whose folded op is not WRITE, ADD_I32 or PAGE_SLICE is
+ *    dropped (keep_item, core/algo/decay_to_item.hpp:14-46); without the flag every group is kept
+ *  - the kept groups of job j come out in key order: a head at (kept items of its own run before it)
+ *    + for every other run (kept items before its bound there)
+ * A record (tkv_amq_merge_item): src = the head's run << TKV_AMQ_LEVELS_SRC_SHIFT | its global index in
+ * that run's arrays (bits 0..55); i32 the folded integer if COMBINED, else 0; op the resolved op (an
+ * empty value: NOOP); flags the two value flags; reserved 0.  With n_runs == 2 every output equals
+ * tkv_amq_merge_leaves' but for the position of the run bit in src.
+ * tkv_amq_merge_counts, with meanings that are tkv_amq_merge_leaves' when n_runs == 2: newer_count
+ * items read of run 0; older_count items read of runs 1 and up; pair_count shadowed items;
+ * combined_count groups whose value is COMBINED; bad_combine_count bad combinations, once each;
+ * dropped_count groups dropped by decay; out_count groups kept.
+ * d_out_begin, d_items, out_capacity, d_needed, d_counts: as tkv_amq_merge_leaves has them --
+ * d_out_begin exact whatever out_capacity is, a record at or past out_capacity not written, *d_needed
+ * the total, no atomic on an output position.  Asynchronous on `stream`: a fixed linear chain of
+ * launches, no allocation, no synchronisation, no copy; capturable.  n_jobs == 0 writes d_out_begin[0]
+ * = 0 and *d_needed = 0.
+ * tkv_amq_merge_levels_ws_bytes (host): at least 16, monotone in each argument, 0 for counts the call
+ * refuses (n_runs 0 or above TKV_AMQ_MERGE_MAX_RUNS, n_jobs or n_items_total above 0xffffffff).
+ * InvalidArgument, judged before a device is looked for: n_runs 0 or above 8; null runs; unknown flag
+ * bits; any run failing tkv_amq_merge_leaves' checks of a run (n_items above 0xffffffff, null keys
+ * with n_items > 0, null values with n_items > 0 and values_bytes > 0, a fixed form with stride 0, a
+ * null d_begin with n_jobs > 0); n_jobs or the runs' items in all above 0xffffffff; a null
+ * d_out_begin, a null d_items with out_capacity > 0, d_items not 16-byte aligned, d_needed, d_counts or
+ * d_out_begin not 8-byte aligned; with n_jobs > 0 a null workspace, one below _ws_bytes or not 16-byte
+ * aligned.  A valid call on a machine without a device returns Unavailable. */
+#define TKV_AMQ_MERGE_MAX_RUNS 8u
+/* tkv_amq_merge_item.src as tkv_amq_merge_levels writes it: bits 56..63 the run (0 = newest),
+ * bits 0..55 the item's global index in that run's arrays */
+#define TKV_AMQ_LEVELS_SRC_SHIFT 56
+
+uint64_t tkv_amq_merge_levels_ws_bytes(uint64_t n_jobs, uint32_t n_runs, uint64_t n_items_total);
+int tkv_amq_merge_levels(const tkv_amq_merge_run* runs, uint32_t n_runs, uint64_t n_jobs, uint32_t flags,
+                         uint64_t* d_out_begin, tkv_amq_merge_item* d_items, uint64_t out_capacity,
+                         uint64_t* d_needed, tkv_amq_merge_counts* d_counts,
+                         void* d_workspace, uint64_t workspace_bytes, void* stream);
+
+/* tkv_amq_gather_merged over a run table: the bytes of a batch of tkv_amq_merge_levels records.
+ * Everything said of tkv_amq_gather_merged holds with "either run" read as "any run": n_out =
+ * min(d_out_begin[n_jobs], out_capacity, the runs' items in all) is read on the device; offsets are
+ * exact whatever the capacities; a COMBINED record writes 5 bytes; a record whose run (bits 56..63) is
+ * at or past n_runs, or whose item index is at or past its run's n_items, gives an empty key and an
+ * empty value; fixed key slots (out_key_stride > 0) only when every run is in the fixed form with that
+ * stride; the values always in the offsets form; d_needed_bytes[0], [1] the totals; sixteen lanes per
+ * item, eight bytes per lane and step.  tkv_amq_merge_levels_values_bound (host) bounds the values'
+ * total: values_bytes_total + 4 * n_items_not_in_oldest_run -- a combined value replaces a head's
+ * non-empty value, and a head in the oldest run has nothing below it to combine with.
+ * tkv_amq_gather_levels_ws_bytes (host): at least 16, monotone.
+ * InvalidArgument: as tkv_amq_gather_merged, its checks of a run applied to every run, and n_runs 0
+ * or above 8 or null runs.  A valid call without a device: Unavailable. */
+uint64_t tkv_amq_merge_levels_values_bound(uint64_t values_bytes_total, uint64_t n_items_not_in_oldest_run);
+uint64_t tkv_amq_gather_levels_ws_bytes(uint64_t out_capacity);
+int tkv_amq_gather_levels(const tkv_amq_merge_item* d_items, const uint64_t* d_out_begin, uint64_t n_jobs,
+                          uint64_t out_capacity, const tkv_amq_merge_run* runs, uint32_t n_runs,
                           uint8_t* d_out_keys, uint32_t out_key_stride, uint64_t* d_out_key_offsets,
                           uint64_t out_keys_capacity, uint8_t* d_out_values, uint64_t* d_out_value_offsets,
                           uint64_t out_values_capacity, uint64_t* d_needed_bytes, void* d_workspace,

@@ -26,6 +26,8 @@
 //                                                                          TreeIndex::get_values_host, KeyQuery::get_values
 //   {BatchUpdate} + {PackedLeafPage}      tree/subtree.cpp:170-231, core/algo/merge_compact_edits.hpp:26-148
 //                                                                          merge_leaves
+//   InMemoryNode::push_levels_to_merge    tree/in_memory_node.cpp:827-866, merge_compact_edits over K levels
+//                                                                          merge_levels
 //
 // The single-leaf functions take the leaf's keys as host string views (the reference's
 // `items` range of EditView keys, tombstones included) and fill a host page payload
@@ -2089,6 +2091,79 @@ inline Status merge_leaves(const tkv_amq_merge_run& newer, const tkv_amq_merge_r
                              k_cap, out.values.get(), out.value_offsets.get<u64>(), v_cap, nullptr, ws.get(),
                              ws.size(), nullptr);
   if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_gather_merged");
+  out.begin.assign(n_jobs + 1, 0);
+  // (blocking copies on the null stream: they wait for the merge and the gather)
+  if (hipMemcpy(out.begin.data(), out.out_begin.get(), 8 * (n_jobs + 1), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&out.counts, tallies.get(), sizeof(out.counts), hipMemcpyDeviceToHost) != hipSuccess)
+    return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy merge results");
+  out.n_items = out.begin.back();
+  out.key_bytes = out.n_items * out.key_stride;
+  if ((!fixed && hipMemcpy(&out.key_bytes, out.key_offsets.get<u64>() + out.n_items, 8, hipMemcpyDeviceToHost) != hipSuccess) ||
+      hipMemcpy(&out.value_bytes, out.value_offsets.get<u64>() + out.n_items, 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy merge sizes");
+  return OkStatus();
+}
+
+// ---------------------------------------------------------------------------------------
+// node merge: merge_compact_edits over the K levels InMemoryNode::push_levels_to_merge pushes
+// (tree/in_memory_node.cpp:827-866; core/algo/merge_compact_edits.hpp:26-148), for a batch of key
+// ranges, on the device (tkv_amq_merge_levels, tkv_amq_gather_levels)
+// ---------------------------------------------------------------------------------------
+// Job j merges items runs[s].d_begin[j .. j + 1) of every run s, runs[0] the newest, each strictly
+// ascending: the newest item of a key stands, an ADD_I32 is folded through the older items of its key
+// while it stays one, and with decay_to_items tombstones and no-ops are dropped.  The counterpart of
+// merge_leaves: the outputs are sized from the inputs, the counts and out_begin are copied back.
+inline Status merge_levels(const tkv_amq_merge_run* runs, u32 n_runs, u64 n_jobs, bool decay_to_items,
+                           MergedLeaves& out)
+{
+  out.begin.assign(1, 0);
+  out.n_items = out.key_bytes = out.value_bytes = 0;
+  out.counts = tkv_amq_merge_counts{};
+  if (!runs || n_runs == 0 || n_runs > TKV_AMQ_MERGE_MAX_RUNS)
+    return Status::from(TKV_AMQ_INVALID_ARGUMENT, "merge_levels: 1 to 8 runs");
+  u64 cap = 0, values_bytes = 0;
+  bool fixed = true;
+  for (u32 s = 0; s < n_runs; ++s) {
+    const tkv_amq_merge_run& r = runs[s];
+    if ((!r.key_offsets && !r.key_stride) || (!r.value_offsets && !r.value_stride))
+      return Status::from(TKV_AMQ_INVALID_ARGUMENT, "merge_levels: a fixed form with stride 0");
+    if (r.n_items > 0xffffffffull) return Status::from(TKV_AMQ_INVALID_ARGUMENT, "merge_levels: too many items");
+    cap += r.n_items;
+    values_bytes += r.values_bytes;
+    fixed = fixed && !r.key_offsets && r.key_stride == runs[0].key_stride;
+  }
+  const u64 ws_bytes = tkv_amq_merge_levels_ws_bytes(n_jobs, n_runs, cap);
+  if (ws_bytes == 0) return Status::from(TKV_AMQ_INVALID_ARGUMENT, "merge_levels: too many jobs or items");
+  if (tkv_amq_device_count() == 0) return Status::from(TKV_AMQ_UNAVAILABLE, "no HIP device");
+  out.key_stride = fixed ? runs[0].key_stride : 0;
+  u64 k_cap = 0;
+  for (u32 s = 0; s < n_runs; ++s) {
+    const tkv_amq_merge_run& r = runs[s];
+    u64 bytes = r.n_items * r.key_stride;
+    if (r.key_offsets && r.n_items &&
+        hipMemcpy(&bytes, r.key_offsets + r.n_items, 8, hipMemcpyDeviceToHost) != hipSuccess)
+      return Status::from(TKV_AMQ_INTERNAL, "hipMemcpy key offsets");
+    k_cap += bytes;
+  }
+  const u64 v_cap = tkv_amq_merge_levels_values_bound(values_bytes, cap - runs[n_runs - 1].n_items);
+  const u64 gather_ws = tkv_amq_gather_levels_ws_bytes(cap);
+  DeviceBuffer ws, tallies;
+  if (!ws.resize(std::max(ws_bytes, gather_ws)) || !tallies.resize(sizeof(tkv_amq_merge_counts)) ||
+      !out.items.resize(sizeof(tkv_amq_merge_item) * cap) || !out.out_begin.resize(8 * (n_jobs + 1)) ||
+      !out.keys.resize(k_cap) || (!fixed && !out.key_offsets.resize(8 * (cap + 1))) || !out.values.resize(v_cap) ||
+      !out.value_offsets.resize(8 * (cap + 1)))
+    return Status::from(TKV_AMQ_RESOURCE_EXHAUSTED, "hipMalloc");
+  if (hipMemset(tallies.get(), 0, sizeof(tkv_amq_merge_counts)) != hipSuccess)
+    return Status::from(TKV_AMQ_INTERNAL, "hipMemset counters");
+  int st = tkv_amq_merge_levels(runs, n_runs, n_jobs, decay_to_items ? TKV_AMQ_MERGE_DECAY_TO_ITEMS : 0u,
+                                out.out_begin.get<u64>(), out.items.get<tkv_amq_merge_item>(), cap, nullptr,
+                                tallies.get<tkv_amq_merge_counts>(), ws.get(), ws.size(), nullptr);
+  if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_merge_levels");
+  st = tkv_amq_gather_levels(out.items.get<tkv_amq_merge_item>(), out.out_begin.get<u64>(), n_jobs, cap, runs, n_runs,
+                             out.keys.get(), out.key_stride, fixed ? nullptr : out.key_offsets.get<u64>(), k_cap,
+                             out.values.get(), out.value_offsets.get<u64>(), v_cap, nullptr, ws.get(), ws.size(),
+                             nullptr);
+  if (st != TKV_AMQ_OK) return Status::from(st, "tkv_amq_gather_levels");
   out.begin.assign(n_jobs + 1, 0);
   // (blocking copies on the null stream: they wait for the merge and the gather)
   if (hipMemcpy(out.begin.data(), out.out_begin.get(), 8 * (n_jobs + 1), hipMemcpyDeviceToHost) != hipSuccess ||

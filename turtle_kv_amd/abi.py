@@ -103,6 +103,8 @@ EXPORTS = [
     "tkv_amq_get_values", "tkv_amq_gather_values",
     "tkv_amq_merge_leaves_ws_bytes", "tkv_amq_merge_leaves", "tkv_amq_merge_values_bound",
     "tkv_amq_gather_merged_ws_bytes", "tkv_amq_gather_merged",
+    "tkv_amq_merge_levels_ws_bytes", "tkv_amq_merge_levels", "tkv_amq_merge_levels_values_bound",
+    "tkv_amq_gather_levels_ws_bytes", "tkv_amq_gather_levels",
 ]
 
 # tkv_amq_build_route: TKV_AMQ_ROUTE_* (a Bloom batch's route, or a VQF batch's decide stage),
@@ -186,6 +188,9 @@ MERGE_COUNTS_FIELDS = ("newer_count", "older_count", "pair_count", "combined_cou
 MERGE_COUNTS_DTYPE = np.dtype([(n, "<u8") for n in MERGE_COUNTS_FIELDS])
 assert MERGE_COUNTS_DTYPE.itemsize == 56
 MERGE_SRC_OLDER = 1 << 63
+# tkv_amq_merge_levels: the runs of one call at most, and where a record's src holds its run
+MERGE_MAX_RUNS = 8
+LEVELS_SRC_SHIFT = 56
 
 
 class MergeRun(ctypes.Structure):
@@ -398,6 +403,19 @@ def lib(build_if_missing: bool = True):
         L.tkv_amq_gather_merged_ws_bytes.argtypes = [u64]
         L.tkv_amq_gather_merged.restype = i32
         L.tkv_amq_gather_merged.argtypes = [vp, vp, u64, u64, prun, prun, vp, u32, vp, u64, vp, vp, u64, vp,
+                                            vp, u64, vp]
+    if hasattr(L, "tkv_amq_merge_levels"):
+        prun = ctypes.POINTER(MergeRun)
+        L.tkv_amq_merge_levels_ws_bytes.restype = u64
+        L.tkv_amq_merge_levels_ws_bytes.argtypes = [u64, u32, u64]
+        L.tkv_amq_merge_levels.restype = i32
+        L.tkv_amq_merge_levels.argtypes = [prun, u32, u64, u32, vp, vp, u64, vp, vp, vp, u64, vp]
+        L.tkv_amq_merge_levels_values_bound.restype = u64
+        L.tkv_amq_merge_levels_values_bound.argtypes = [u64, u64]
+        L.tkv_amq_gather_levels_ws_bytes.restype = u64
+        L.tkv_amq_gather_levels_ws_bytes.argtypes = [u64]
+        L.tkv_amq_gather_levels.restype = i32
+        L.tkv_amq_gather_levels.argtypes = [vp, vp, u64, u64, prun, u32, vp, u32, vp, u64, vp, vp, u64, vp,
                                             vp, u64, vp]
     if hasattr(L, "tkv_amq_bloom_route"):
         L.tkv_amq_bloom_route_ws_bytes.restype = u64

@@ -86,11 +86,23 @@ struct KeyArray {
 enum KeyOrderMode : int { kOrder16 = 0, kOrder24 = 1, kOrderAny = 2 };
 
 // (host side: the entry points choose the kernel with it; static, so the library exports nothing new)
+// Over a table of n >= 1 arrays any of which may be searched for a key of any other: the fixed modes
+// only when every one of them qualifies.
+static inline KeyOrderMode key_order_mode(const KeyArray* ks, uint32_t n)
+{
+  bool fixed = true;
+  uintptr_t all = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    fixed = fixed && !ks[i].offsets && ks[i].stride == ks[0].stride;
+    all |= reinterpret_cast<uintptr_t>(ks[i].base);
+  }
+  return fixed && ks[0].stride == 16 && !(all & 15) ? kOrder16 : fixed && ks[0].stride == 24 && !(all & 7) ? kOrder24 : kOrderAny;
+}
+
 static inline KeyOrderMode key_order_mode(const KeyArray& q, const KeyArray& k)
 {
-  const bool fixed = !q.offsets && !k.offsets && q.stride == k.stride;
-  const uintptr_t both = reinterpret_cast<uintptr_t>(q.base) | reinterpret_cast<uintptr_t>(k.base);
-  return fixed && q.stride == 16 && !(both & 15) ? kOrder16 : fixed && q.stride == 24 && !(both & 7) ? kOrder24 : kOrderAny;
+  const KeyArray both[2] = {q, k};
+  return key_order_mode(both, 2);
 }
 
 // The query of one lane (key i of `qs`), and its order against key i of an array of the same mode.

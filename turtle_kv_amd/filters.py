@@ -1659,6 +1659,107 @@ def merge_leaves(newer: KeyBatch, newer_values: KeyBatch, newer_begin, older: Ke
 
 
 # ---------------------------------------------------------------------------------------
+# node merge: a batch of K-way merges (the incoming batch over the update-buffer levels) on the device
+# ---------------------------------------------------------------------------------------
+def merge_levels_workspace_bytes(n_jobs: int, n_runs: int, n_items_total: int) -> int:
+    """tkv_amq_merge_levels_ws_bytes (0: counts the call refuses)."""
+    return int(abi.lib().tkv_amq_merge_levels_ws_bytes(int(n_jobs), int(n_runs), int(n_items_total)))
+
+
+def gather_levels_workspace_bytes(out_capacity: int) -> int:
+    """tkv_amq_gather_levels_ws_bytes."""
+    return int(abi.lib().tkv_amq_gather_levels_ws_bytes(int(out_capacity)))
+
+
+def merge_levels_values_bound(values_bytes_total: int, n_items_not_in_oldest_run: int) -> int:
+    """tkv_amq_merge_levels_values_bound: the merged values' bytes at most."""
+    return int(abi.lib().tkv_amq_merge_levels_values_bound(int(values_bytes_total), int(n_items_not_in_oldest_run)))
+
+
+def _run_table(runs):
+    """A list of abi.MergeRun (the newest first) as the contiguous host array the library takes."""
+    return (abi.MergeRun * max(len(runs), 1))(*runs)
+
+
+def merge_levels_device(runs, n_jobs: int, d_out_begin, d_items, out_capacity: int, workspace, d_needed=None,
+                        flags: int = 0, d_counts=None, stream=None) -> None:
+    """The launches alone (tkv_amq_merge_levels), capturable: `runs` a list of 1..8 merge_run structs,
+    the newest first; the other arguments as merge_leaves_device has them, with a workspace of
+    merge_levels_workspace_bytes.  A record's src holds its run in bits 56..63."""
+    _require_device()
+    st = abi.lib().tkv_amq_merge_levels(
+        _run_table(runs), len(runs), int(n_jobs), int(flags), _ptr(d_out_begin), _ptr(d_items), int(out_capacity),
+        _ptr(d_needed), _ptr(d_counts), _ptr(workspace), 0 if workspace is None else int(workspace.numel()),
+        _stream_handle(stream))
+    abi.check(st, "tkv_amq_merge_levels")
+
+
+def gather_levels_device(d_items, d_out_begin, n_jobs: int, out_capacity: int, runs, d_out_keys,
+                         out_key_stride: int, d_out_key_offsets, out_keys_capacity: int, d_out_values,
+                         d_out_value_offsets, out_values_capacity: int, workspace, d_needed_bytes=None,
+                         stream=None) -> None:
+    """The launches alone (tkv_amq_gather_levels), capturable behind merge_levels_device: as
+    gather_merged_device, over the merge's list of runs."""
+    _require_device()
+    st = abi.lib().tkv_amq_gather_levels(
+        _ptr(d_items), _ptr(d_out_begin), int(n_jobs), int(out_capacity), _run_table(runs), len(runs),
+        _ptr(d_out_keys), int(out_key_stride), _ptr(d_out_key_offsets), int(out_keys_capacity), _ptr(d_out_values),
+        _ptr(d_out_value_offsets), int(out_values_capacity), _ptr(d_needed_bytes), _ptr(workspace),
+        0 if workspace is None else int(workspace.numel()), _stream_handle(stream))
+    abi.check(st, "tkv_amq_gather_levels")
+
+
+def merge_levels(runs, *, decay: bool = False, stream=None) -> MergeResult:
+    """The merge of K levels for a batch of key ranges (tkv_amq_merge_levels, then tkv_amq_gather_levels):
+    `runs` is a list of 1..8 (keys: KeyBatch, values: KeyBatch, begin) triples, the newest level first;
+    job j merges items [begin[j], begin[j + 1]) of every run -- each strictly ascending -- as the
+    reference's merge_compact_edits does over the levels InMemoryNode::push_levels_to_merge pushes: the
+    newest item of a key stands, an ADD_I32 is folded through the older items of its key, and with
+    decay=True tombstones and no-ops are dropped.  The counterpart of merge_leaves: the outputs are sized
+    from the inputs, and the record count and `counts` are read back, which synchronises."""
+    torch = _torch()
+    _require_device()
+    if not 1 <= len(runs) <= abi.MERGE_MAX_RUNS:
+        raise TkvAmqError(abi.INVALID_ARGUMENT, "merge_levels: 1 to 8 runs")
+    dev = runs[-1][0].data.device
+    begins = [_begin_tensor(b, dev, f"begin of run {r}") for r, (_, _, b) in enumerate(runs)]
+    if any(b.numel() != begins[0].numel() for b in begins):
+        raise TkvAmqError(abi.INVALID_ARGUMENT, "merge_levels: the begin arrays differ in length")
+    n_jobs = int(begins[0].numel()) - 1
+    table = [merge_run(k, v, b) for (k, v, _), b in zip(runs, begins)]
+    keys, values = [k for k, _, _ in runs], [v for _, v, _ in runs]
+    cap = sum(k.n for k in keys)
+    ws_bytes = max(merge_levels_workspace_bytes(n_jobs, len(runs), cap), gather_levels_workspace_bytes(cap))
+    if merge_levels_workspace_bytes(n_jobs, len(runs), cap) == 0:
+        raise TkvAmqError(abi.INVALID_ARGUMENT, "merge_levels: too many jobs or items")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out_begin = torch.empty(n_jobs + 1, dtype=torch.int64, device=dev)
+    items = torch.empty(max(cap, 1) * 16, dtype=torch.uint8, device=dev)
+    counts = MergeCounts(dev)
+    merge_levels_device(table, n_jobs, out_begin, items, cap, ws, None, abi.MERGE_DECAY_TO_ITEMS if decay else 0,
+                        counts.counts, stream)
+    stride = keys[0].stride
+    fixed = all(k.offsets is None and k.stride == stride for k in keys)
+    k_cap = cap * stride if fixed else sum(k.n * k.stride if k.offsets is None else int(k.data.numel()) for k in keys)
+    v_cap = merge_levels_values_bound(sum(int(v.data.numel()) for v in values), cap - keys[-1].n)
+    out_keys = torch.empty(max(k_cap, 1), dtype=torch.uint8, device=dev)
+    out_vals = torch.empty(max(v_cap, 1), dtype=torch.uint8, device=dev)
+    k_offs = None if fixed else torch.empty(cap + 1, dtype=torch.int64, device=dev)
+    v_offs = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+    gather_levels_device(items, out_begin, n_jobs, cap, table, out_keys, stride if fixed else 0, k_offs, k_cap,
+                         out_vals, v_offs, v_cap, ws, None, stream)
+    _hold(stream, *begins, ws, out_begin, items, out_keys, out_vals, k_offs, v_offs, counts.counts)
+    (stream if stream is not None else torch.cuda.current_stream()).synchronize()
+    n_out = int(out_begin[n_jobs].item())
+    if fixed:
+        out = KeyBatch.fixed(out_keys[:n_out * stride].view(n_out, stride))
+    else:
+        out = KeyBatch.variable(out_keys, k_offs[:n_out + 1])
+    return MergeResult(out, KeyBatch.variable(out_vals, v_offs[:n_out + 1]), out_begin, items[:16 * n_out],
+                       counts.collect())
+
+
+# ---------------------------------------------------------------------------------------
 # single-leaf API (the reference's per-leaf entry points)
 # ---------------------------------------------------------------------------------------
 @dataclass
